@@ -12,7 +12,16 @@ HBM, random-init weights (no network on the box).
 `python bench.py --gpus N` with N > 1 and no torchrun environment launches the N ranks itself
 (torch.distributed.run, one process per GPU, RCCL); it exits non-zero if fewer than N GPUs are visible.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus:
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, W warm-up steps, ONE timed window of exactly
+K steps, the optional `--dump-outputs DIR`, and the JSON line (`value`, `ms_per_step` = that window's).  Everything else below -- the roofline figures,
+the all-reduce time, the CPU baseline, the other target form, the H2D-inclusive and input-stage rates, and 5 timed windows (median) instead of one --
+runs only with `--full`.
+
+`--dump-outputs DIR` writes what the LAST timed step computed as float32 `DIR/<name>.npy` (see `dump_outputs`): pred_boxes, pred_sims, the four losses
+and their sum, and a fixed seeded sample of the updated trainable parameters (and, with the in-line schedule, of their gradients).  Inputs and weights
+are seeded, so two builds run with the same arguments can be compared output for output.
+
+Prints ONE JSON line (rank 0) with the driver's contract plus, with `--full`:
   roofline       -- the dominant op by time (the bias-epilogue GEMM: QKV / out-proj / fc2 / dX, ~30 % of the step; one op =
                     `gemm_pp2_kernel<bias>` + its half-height remainder launch `gemm_pph_kernel<bias>` where the dispatcher
                     splits): algorithmic FLOPs per op / mean op duration, HIP events on the launch stream inside the timed
@@ -89,11 +98,16 @@ except (OSError, ValueError):
     TRAFFIC_NOTE = f"{TRAFFIC_FILE} missing"
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (per window)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / all-reduce HIP events, CPU baseline, the other --targets form, the "
+                         "H2D-inclusive and input-stage rates, and 5 timed windows by default (off: one window, the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--batch", type=int, default=32, help="images per GPU")
     ap.add_argument("--arch", default="owlvit-base-patch16")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -117,9 +131,10 @@ def parse():
                     help="test-only: make the deferred-tail phase of the multi-rank flow fail that way (tests/test_ddp_rccl_gpu.py checks that the in-line line survives)")
     ap.add_argument("--watchdog-seconds", type=float, default=None, help="limit for the deferred-tail phase (default: max(120, 40 x the in-line measurement))")
     ap.add_argument("--no-kernel-events", action="store_true", help="no HIP events around the GEMM / attention launches (overhead A/B)")
-    ap.add_argument("--windows", type=int, default=5,
+    ap.add_argument("--windows", type=int, default=None,
                     help="timed windows of --steps steps each, back to back after ONE warm-up (each bracketed by barrier + synchronize, max over ranks); "
-                         "`value` / `ms_per_step` are the MEDIAN window's, config.window_values lists them all (VERDICT r05 #4: one 0.5 s window cannot resolve 2 %%)")
+                         "`value` / `ms_per_step` are the MEDIAN window's, config.window_values lists them all (VERDICT r05 #4: one 0.5 s window cannot resolve 2 %%). "
+                         "Default: 5 with --full, else 1")
     ap.add_argument("--pretranspose", type=int, choices=(0, 1), default=0,
                     help="0 (default, = the product): the backward makes its weight transposes itself; 1: the forward launches them on their own stream "
                          "(models.OwlViT.pretranspose; measured no faster: A/B, profiles/r06_tail.md)")
@@ -133,7 +148,14 @@ def parse():
     ap.add_argument("--encoder-streams", type=int, default=2,
                     help="sub-batches of the encoder forward / dX-only backward, one HIP stream each (OwlViT(encoder_streams=...)); 1 = one stream "
                          "(what the rocprofv3 profiles are taken with: kernel durations are then exclusive)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    if not args.full:                   # a plain run: the headline alone
+        args.no_cpu_baseline = True
+        args.no_compare = True
+        args.no_kernel_events = True
+    return args
 
 
 def self_launch(args):
@@ -151,10 +173,11 @@ def self_launch(args):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
-def synth_batches(cfg, B, device, rank, n_batches=2, seed=1234):
+def synth_batches(cfg, B, device, rank, n_batches=2, seed=1234, host_copies=True):
     """CLIP-normalised uniform-u8 pixels (f32, as the reference's DataLoader yields) + 1..16 boxes/image, already on the device.
     Images, targets and weights all come from the repo's counter-based RNG (bit-identical on every box; seed + rank
-    for the data, identical weights on every rank)."""
+    for the data, identical weights on every rank).  host_copies=False leaves out the host-side copies (pinned f32 images, uint8 pixels,
+    host targets) that only the H2D-inclusive and input-stage measurements of --full read."""
     from owl_vit_object_detection_amd import synth
     from owl_vit_object_detection_amd.matcher import PackedTargets
     out = []
@@ -164,6 +187,9 @@ def synth_batches(cfg, B, device, rank, n_batches=2, seed=1234):
         lab_l = [torch.from_numpy(l).to(device) for l in labels]          # ref main.py:78-79: labels.to(device), boxes.to(device)
         box_l = [torch.from_numpy(b).to(device) for b in boxes]
         tg = PackedTargets(lab_l, box_l, device, cfg.n_classes)
+        if not host_copies:
+            out.append(dict(img=img.contiguous(), packed=tg, labels=lab_l, boxes=box_l, labels_np=labels))
+            continue
         img_host = torch.from_numpy(synth.make_images(cfg, B, seed + rank, first=k * B)).pin_memory()      # what a DataLoader(pin_memory=True) hands over
         # the same pixels as the uint8 levels they were normalised from (host, NOT pinned: what a DataLoader of raw images yields) + host targets:
         # the feed of the product-level input stage (preprocess.DevicePrefetcher)
@@ -235,6 +261,32 @@ def cpu_baseline(cfg, steps, batch8=False):
         out["value"] = round(max(1.0 / m1, 8.0 / m8), 4)
         out["sample"] += f"; batch 8: median {m8:.2f} s/step over {n8} steps after {w8} warm-ups (value = the better of the two)"
     return out
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000     # all files of one --dump-outputs together
+DUMP_SAMPLE_ELEMS = 3 * 1000 * 1000      # an array with more elements is written as a fixed seeded sample of this many (flattened, ascending index)
+DUMP_SAMPLE_SEED = 20240611
+
+
+def dump_outputs(outdir, arrays):
+    """Write each named tensor as float32 `outdir/<name>.npy`.  An array of more than DUMP_SAMPLE_ELEMS elements is replaced by `<name>_sample.npy`: the
+    elements at DUMP_SAMPLE_ELEMS indices drawn without replacement by numpy's default_rng(DUMP_SAMPLE_SEED) from its flattened form, in ascending
+    order -- the same indices for the same element count on every run.  Returns {file name: shape}."""
+    os.makedirs(outdir, exist_ok=True)
+    written, total = {}, 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(t.numel(), DUMP_SAMPLE_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name = name + "_sample"
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise ValueError(f"--dump-outputs: {name} would take the dump past {DUMP_BUDGET_BYTES} bytes")
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+    return written
 
 
 EVENT_EVERY = 10
@@ -327,7 +379,7 @@ def main():
                                                     "load": staticmethod(_L.load)})
     slow_tiles = torch.zeros(1, dtype=torch.int32, device=dev)      # attention forward: (wave, key tile) pairs that left the fast path (csrc/attention_fwd.hip)
     ops.ATTN_SLOW_TILES = slow_tiles
-    batches = synth_batches(cfg, B, dev, rank)
+    batches = synth_batches(cfg, B, dev, rank, host_copies=args.full)
     if "castimg" in ablate_names:
         for bt in batches:
             bt["img"] = bt["img"].to(torch.bfloat16)
@@ -367,7 +419,7 @@ def main():
         ops.attention_bwd = kt.wrap(ops.attention_bwd, classify_attn_bwd)
 
     ar_events = []
-    if world > 1 or os.environ.get("OWL_FORCE_DIST", "0") == "1":
+    if args.full and (world > 1 or os.environ.get("OWL_FORCE_DIST", "0") == "1"):
         orig_ar = ddp.allreduce_flat
 
         def timed_ar(flat_grad, group=None):
@@ -382,7 +434,10 @@ def main():
     h2d = [False]          # True: the step starts from f32 images in pinned HOST memory and copies them itself, as ref main.py:77 `image.to(device)` does
     feed = [None]          # an iterator of preprocess.DevicePrefetcher: the step takes images AND targets from it (host u8 -> HBM bf16, one batch ahead)
 
-    def step(i, mode):
+    last = {}              # keep=True: what that step computed (--dump-outputs)
+    dump_pending = [bool(args.dump_outputs)]
+
+    def step(i, mode, keep=False):
         bt = batches[i % len(batches)]
         if feed[0] is not None:
             img, lab_f, box_f = next(feed[0])
@@ -396,7 +451,9 @@ def main():
         img = bt["img_host"].to(dev, non_blocking=True) if h2d[0] else bt["img"]
         if args.forward_only:
             with torch.no_grad():
-                model(img)
+                pred_boxes, _, pred_sims, _ = model(img)
+            if keep:
+                last.clear(); last.update(pred_boxes=pred_boxes, pred_sims=pred_sims)
             return None
         opt.zero_grad()
         pred_boxes, _, pred_sims, _ = model(img)
@@ -404,6 +461,8 @@ def main():
             loss = pred_boxes.mean() + pred_sims.mean()
             loss.backward()
             dp.sync_and_step()
+            if keep:
+                last.clear(); last.update(pred_boxes=pred_boxes.detach(), pred_sims=pred_sims.detach(), loss=loss.detach())
             return loss.detach()
         if mode == "lists":
             losses = crit(pred_sims, bt["labels"], pred_boxes, bt["boxes"])       # ref main.py:83
@@ -412,6 +471,9 @@ def main():
         loss = losses["loss_ce"] + losses["loss_bg"] + losses["loss_bbox"] + losses["loss_giou"]
         loss.backward()
         dp.sync_and_step()
+        if keep:
+            last.clear()
+            last.update(pred_boxes=pred_boxes.detach(), pred_sims=pred_sims.detach(), **{k: v.detach() for k, v in losses.items()}, loss=loss.detach())
         return loss.detach()
 
     def set_schedule(overlap):
@@ -446,7 +508,7 @@ def main():
                     model.overlap_tail = not kt.on
                     if kt.on:
                         model.finish()
-                step(base + i, mode)
+                step(base + i, mode, keep=dump_pending[0] and w == max(1, windows) - 1 and i == steps - 1)
             model.encoder_streams = args.encoder_streams
             model.overlap_tail = dp.overlap
             dp.finish()
@@ -464,6 +526,11 @@ def main():
                 lo_hi = (-float(t[1].item()), dt)
             dts.append(dt); lohi.append(lo_hi); slows.append(int(slow_tiles.item()))
             gpu_seconds[0] += dt
+            if dump_pending[0] and w == max(1, windows) - 1 and not args.forward_only:
+                # (copies taken outside the timed window: the measurements --full runs after the headline move the parameters on)
+                last["params"] = model.flat_param.clone()
+                if not model._grad_clean:                      # (a deferred optimizer step has already zeroed the bucket for the next step)
+                    last["grads"] = model.flat_grad.clone()
         k = int(np.argsort(dts)[len(dts) // 2])                # the median window (an actual window, not an average)
         timed_run.rank_seconds = lohi[k]
         timed_run.window_seconds = list(dts)
@@ -599,7 +666,7 @@ def main():
         import threading
         set_schedule(False)
         kt.windows_recorded = args.windows
-        dt_in, slow_in = timed_run(args.targets, args.steps, args.warmup, True, windows=args.windows)
+        dt_in, slow_in = timed_run(args.targets, args.steps, args.warmup, args.full, windows=args.windows)
         eq_in = replicas_equal()
         extra["images_per_sec_inline_schedule"] = round(B * world * args.steps / dt_in, 2)
         line_inline = report(dt_in, slow_in, "in-line", dict(extra))
@@ -651,10 +718,16 @@ def main():
     else:
         set_schedule(want_overlap and not args.forward_only and model.flat_grad.is_cuda)
         kt.windows_recorded = args.windows
-        dt, slow = timed_run(args.targets, args.steps, args.warmup, True, windows=args.windows)
+        dt, slow = timed_run(args.targets, args.steps, args.warmup, args.full, windows=args.windows)
         line = report(dt, slow, SCHED_TAIL if dp.overlap else "in-line", extra)
         if dist_active:
             line["replicas_equal"] = replicas_equal()
+    if dump_pending[0]:
+        dump_pending[0] = False
+        if rank == 0:
+            written = dump_outputs(args.dump_outputs, last)
+            sys.stderr.write(f"bench.py: the last timed step's outputs -> {args.dump_outputs}: {written}\n")
+        last.clear()
     if not args.forward_only and not args.no_compare:
         other_mode = "packed" if args.targets == "lists" else "lists"
         dt_o, _ = timed_run(other_mode, args.steps, 1, False)

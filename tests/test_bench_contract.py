@@ -1,5 +1,6 @@
-"""CPU-side checks of bench.py's bookkeeping (no GPU): the counter-traffic file it quotes as `roofline.traffic` was measured on THESE kernel sources, and the
-`cpu_baseline` leg produces the fields the contract names."""
+"""CPU-side checks of bench.py's bookkeeping (no GPU): the counter-traffic file it quotes as `roofline.traffic` was measured on THESE kernel sources, the
+`cpu_baseline` leg produces the fields the contract names, a plain run measures the headline alone (the rest behind --full), and --dump-outputs writes
+float32 arrays with a fixed seeded sample of the large ones."""
 import json
 import os
 import sys
@@ -38,3 +39,39 @@ def test_cpu_baseline_leg_fields(bench_mod):
     out = bench_mod.cpu_baseline(get_config("tiny"), 5)
     assert out["kind"] == "port" and out["unit"] == "images/sec" and out["value"] > 0 and 1 <= out["cores"] <= (os.cpu_count() or 1)
     assert "AdamW" in out["sample"] and "median" in out["sample"]
+
+
+def test_plain_run_is_the_headline_alone_and_full_keeps_the_rest(bench_mod):
+    """A plain run times ONE window of exactly --steps steps and measures nothing else; --full brings back the 5 windows, HIP events, CPU baseline and the
+    comparison runs, each still switchable off on its own."""
+    a = bench_mod.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.steps, a.warmup, a.windows, a.dump_outputs) == (False, 7, 2, 1, None)
+    assert a.no_cpu_baseline and a.no_compare and a.no_kernel_events
+    f = bench_mod.parse(["--full", "--steps", "7"])
+    assert f.full and f.windows == 5 and not (f.no_cpu_baseline or f.no_compare or f.no_kernel_events)
+    f = bench_mod.parse(["--full", "--no-cpu-baseline", "--no-compare", "--windows", "2"])
+    assert f.no_cpu_baseline and f.no_compare and not f.no_kernel_events and f.windows == 2
+    assert bench_mod.parse(["--windows", "3", "--dump-outputs", "d"]).windows == 3 and bench_mod.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_float32_with_a_fixed_seeded_sample(bench_mod, tmp_path):
+    import numpy as np
+    import torch
+    n_big = bench_mod.DUMP_SAMPLE_ELEMS + 12345
+    big = torch.arange(n_big, dtype=torch.float64).reshape(1, -1)          # (a float64 2-D array: flattened, sampled, written as float32)
+    small = torch.randn(3, 4, 2, dtype=torch.float32)
+    arrays = {"pred_boxes": small, "loss": torch.tensor(1.5, dtype=torch.float32), "params": big, "half": torch.ones(6, dtype=torch.bfloat16)}
+    w1 = bench_mod.dump_outputs(str(tmp_path / "a"), arrays)
+    w2 = bench_mod.dump_outputs(str(tmp_path / "b"), arrays)
+    assert w1 == w2 == {"pred_boxes.npy": [3, 4, 2], "loss.npy": [], "params_sample.npy": [bench_mod.DUMP_SAMPLE_ELEMS], "half.npy": [6]}
+    total = 0
+    for name in w1:
+        x, y = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert x.dtype == np.float32 and np.array_equal(x, y), name
+        total += os.path.getsize(tmp_path / "a" / name)
+    assert total <= bench_mod.DUMP_BUDGET_BYTES
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "pred_boxes.npy"), small.numpy())
+    s = np.load(tmp_path / "a" / "params_sample.npy")
+    assert np.all(np.diff(s) > 0) and s[0] >= 0 and s[-1] < n_big           # ascending, distinct indices of the flattened array (its values ARE the indices)
+    idx = np.sort(np.random.default_rng(bench_mod.DUMP_SAMPLE_SEED).choice(n_big, bench_mod.DUMP_SAMPLE_ELEMS, replace=False))
+    np.testing.assert_array_equal(s, idx.astype(np.float32))

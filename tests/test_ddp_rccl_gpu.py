@@ -48,6 +48,34 @@ def test_bench_refuses_more_gpus_than_visible():
     assert f"only {n} GPU" in r.stderr and "n_gpus" not in r.stdout
 
 
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_exactly_the_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run: one window of exactly --steps timed steps, the headline fields and nothing that --full measures; --dump-outputs writes the last timed
+    step's outputs as float32, and a second run with the same arguments writes the same bits (seeded inputs and weights, deterministic step)."""
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--arch", "tiny", "--batch", "4",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, env=_env(), timeout=500)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = _last_json(r.stdout)
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["config"]["windows"] == 1 and len(out["config"]["window_values"]) == 1
+        assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(4 * 1000.0 / out["ms_per_step"], rel=2e-3)
+        assert out["unit"] == "images/sec" and out["higher_is_better"] is True and out["dtype"] == "bf16" and out["metric"].startswith("train images/sec")
+        assert not {"cpu_baseline", "roofline", "roofline_other", "allreduce_ms"} & set(out)
+        assert not {"images_per_sec_packed_targets", "images_per_sec_incl_h2d", "images_per_sec_from_host_u8_product"} & set(out["config"])
+        files = sorted(os.listdir(d))
+        assert {"pred_boxes.npy", "pred_sims.npy", "loss.npy", "loss_ce.npy", "loss_bg.npy", "loss_bbox.npy", "loss_giou.npy", "params.npy",
+                "grads.npy"} == set(files), files
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["pred_boxes.npy"].shape[0] == 4 and arrs["pred_boxes.npy"].shape[-1] == 4 and np.abs(arrs["grads.npy"]).max() > 0
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 1000 * 1000
+        outs.append(arrs)
+    for f in outs[0]:
+        assert np.array_equal(outs[0][f], outs[1][f]), f
+
+
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("schedule", ["in-line", "overlap"])
 def test_bench_single_forced_rccl_rank_reports_the_collective(schedule):
@@ -55,7 +83,7 @@ def test_bench_single_forced_rccl_rank_reports_the_collective(schedule):
     one: backward + RCCL + AdamW on the model's tail stream while the next step's sub-batch streams already run the frozen prefix); batch 8 so that the
     encoder runs its two sub-batch streams beside them."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "1", "--arch", "small",
-                        "--batch", "8", "--no-cpu-baseline"] + (["--overlap"] if schedule == "overlap" else []),
+                        "--batch", "8", "--full", "--no-cpu-baseline"] + (["--overlap"] if schedule == "overlap" else []),
                        capture_output=True, text=True, env=_env(OWL_FORCE_DIST="1"), timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _last_json(r.stdout)
