@@ -32,9 +32,9 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even.  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop).  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
-#define OWL_ABI_VERSION 6
+#define OWL_ABI_VERSION 7
 const char* owl_last_error(void);
 int owl_abi_version(void);
 
@@ -147,6 +147,24 @@ int owl_push_pull_loss_bwd(void* stream, const float* g4, const int64_t* target_
  * workspace: device scratch of owl_postprocess_workspace() bytes (16-byte aligned); `bytes` is a HOST pointer.     */
 int owl_postprocess_workspace(int64_t B, int64_t P, int64_t* bytes);
 int owl_postprocess(void* stream, const float* boxes, const float* sims, void* workspace, int64_t ws_bytes, float* out_boxes, float* out_scores, int64_t* out_classes, int64_t* out_patch, int* out_count, int64_t B, int64_t P, int64_t C, int64_t max_out, float conf_thr, float iou_thr, int route);
+
+/* ---- COCO bbox mAP of the eval loop, on device (ref main.py:31,120-128,144-147; src/train_util.py:37-64 -> torchmetrics
+ * MeanAveragePrecision(iou_type="bbox", class_metrics=True) -> the pycocotools COCOeval protocol evaluateImg / accumulate).  ABI 7.
+ * The protocol's constants come from the caller as device arrays and are never re-derived in device code: iou_thr f64 [10] (linspace(0.5, 0.95, 10)),
+ * area_rng f64 [4][2] = {lo, hi} of all / small / medium / large, rec_thr f64 [101] (linspace(0, 1, 101)), max_dets i32 [3] = {1, 10, 100}, eps = spacing(1).
+ * The counts 10 / 4 / 3 / 101 and the cut to 100 detections per (image, class) are part of the record layout.
+ * owl_map_match -- one launch per metric update, no host sync.  det_boxes [B,K,4] f32 xyxy, det_scores [B,K], det_labels [B,K] i64, det_counts [B] i32 (slots
+ * past the count and labels outside [0, C) are padding: the batched PostProcess layout pads with -1); gt_boxes [B,G,4], gt_labels [B,G] i64, gt_counts [B];
+ * scale [B,2] f32 = (sx, sy) multiplied onto x / y of both box sets in f32 (1 for pixel boxes, width / height for normalised ones, ref src/util.py:94-97).
+ * Detections need not be sorted: the kernel ranks the detections of an (image, class) by descending score, ties by slot, and keeps 100.
+ * Per detection slot: rec_score [B,K] f32, rec_label [B,K] i64 (-1: the slot is no record -- padding, label out of range, rank >= 100), rec_rank [B,K] i32
+ * (rank within its image and class), rec_mask [B,K,4] i32, one word per area range: bit t = matched at IoU threshold t, bit 10 + t = ignored at t.
+ * npig [B,C,4] i32 = ground truths of the class inside the area range.  K <= 1024, G <= 256.
+ * owl_map_accumulate -- one launch per compute().  rec_rank [N] / rec_mask [N,4]: the records of all updates, ordered by class, inside a class by descending
+ * score, stable in arrival order; seg i64 [C+1] = class boundaries in that order; npig i32 [C,4] summed over the images.
+ * -> precision f64 [10,101,C,4,3], recall f64 [10,C,4,3]; -1 where a (class, area range) has no ground truth.  No scratch. */
+int owl_map_match(void* stream, const float* det_boxes, const float* det_scores, const int64_t* det_labels, const int* det_counts, const float* gt_boxes, const int64_t* gt_labels, const int* gt_counts, const float* scale, const double* iou_thr, const double* area_rng, float* rec_score, int64_t* rec_label, int* rec_rank, int* rec_mask, int* npig, int64_t B, int64_t K, int64_t G, int64_t C);
+int owl_map_accumulate(void* stream, const int* rec_rank, const int* rec_mask, const int64_t* seg, const int* npig, const double* rec_thr, const int* max_dets, double eps, double* precision, double* recall, int64_t N, int64_t C);
 
 /* ---- the one collective of the path: in-place SUM of the flat f32 gradient bucket over the data-parallel ranks on `stream`, through the
  * CALLER's RCCL communicator (`rccl_comm` = an `ncclComm_t`).  For hosts without PyTorch; this repo's Python host issues the same collective through

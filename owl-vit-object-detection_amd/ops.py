@@ -264,6 +264,64 @@ def postprocess(boxes, sims, max_out, conf_thr, iou_thr, route="torchvision_gpu"
     return out_boxes, out_classes, out_scores, out_patch, counts
 
 
+# ---- COCO bbox mAP of the eval loop (csrc/metrics.hip).  The protocol's constants are made ONCE on the host, exactly as pycocotools makes them,
+# and handed to the kernels as arrays: device code never re-derives a threshold.
+MAP_T, MAP_R, MAP_A, MAP_M = 10, 101, 4, 3
+_map_consts = {}
+
+
+def map_constants(dev):
+    """-> dict of device tensors: iou_thr f64 [10], rec_thr f64 [101], area_rng f64 [4,2] (all / small / medium / large), max_dets i32 [3]; eps (float)."""
+    dev = torch.device(dev)
+    if dev not in _map_consts:
+        import numpy as np
+        _map_consts[dev] = dict(
+            iou_thr=torch.from_numpy(np.linspace(0.5, 0.95, 10)).to(dev), rec_thr=torch.from_numpy(np.linspace(0.0, 1.0, 101)).to(dev),
+            area_rng=torch.tensor([[0.0, 1e10], [0.0, 32.0 ** 2], [32.0 ** 2, 96.0 ** 2], [96.0 ** 2, 1e10]], dtype=torch.float64, device=dev),
+            max_dets=torch.tensor([1, 10, 100], dtype=torch.int32, device=dev), eps=float(np.spacing(1)))
+    return _map_consts[dev]
+
+
+def map_match(det_boxes, det_scores, det_labels, det_counts, gt_boxes, gt_labels, gt_counts, scale, n_classes):
+    """owl_map_match: one launch, no host sync.  det_boxes [B,K,4] f32 xyxy, det_scores [B,K] f32, det_labels [B,K] i64 (-1 pad), det_counts [B] i32,
+    gt_boxes [B,G,4], gt_labels [B,G] i64, gt_counts [B] i32, scale [B,2] f32 -> (score [B,K], label [B,K] i64 (-1: no record), rank [B,K] i32,
+    mask [B,K,4] i32 (bit t matched, bit 10 + t ignored, per area range), npig [B,C,4] i32)."""
+    _chk(det_boxes, torch.float32, "det_boxes"); _chk(det_scores, torch.float32, "det_scores"); _chk(det_labels, torch.int64, "det_labels")
+    _chk(det_counts, torch.int32, "det_counts"); _chk(gt_boxes, torch.float32, "gt_boxes"); _chk(gt_labels, torch.int64, "gt_labels")
+    _chk(gt_counts, torch.int32, "gt_counts"); _chk(scale, torch.float32, "scale")
+    B, K = det_scores.shape
+    G = gt_labels.shape[1]
+    if det_boxes.shape != (B, K, 4) or det_labels.shape != (B, K) or det_counts.shape != (B,) or gt_boxes.shape != (B, G, 4) \
+            or gt_labels.shape != (B, G) or gt_counts.shape != (B,) or scale.shape != (B, 2):
+        raise ValueError(f"map_match: inconsistent shapes {tuple(det_boxes.shape)} {tuple(det_scores.shape)} {tuple(det_labels.shape)} {tuple(det_counts.shape)} "
+                         f"{tuple(gt_boxes.shape)} {tuple(gt_labels.shape)} {tuple(gt_counts.shape)} {tuple(scale.shape)}")
+    dev, C = det_scores.device, int(n_classes)
+    k = map_constants(dev)
+    score = torch.empty(B, K, dtype=torch.float32, device=dev)
+    label = torch.empty(B, K, dtype=torch.int64, device=dev)
+    rank = torch.empty(B, K, dtype=torch.int32, device=dev)
+    mask = torch.empty(B, K, MAP_A, dtype=torch.int32, device=dev)
+    npig = torch.empty(B, max(C, 0), MAP_A, dtype=torch.int32, device=dev)
+    _lib.call("owl_map_match", stream(), det_boxes, det_scores, det_labels, det_counts, gt_boxes, gt_labels, gt_counts, scale, k["iou_thr"], k["area_rng"],
+              score, label, rank, mask, npig, B, K, G, C)
+    return score, label, rank, mask, npig
+
+
+def map_accumulate(rank, mask, seg, npig, n_classes):
+    """owl_map_accumulate: rank [N] i32 / mask [N,4] i32 = the records ordered by class, then by descending score (stable); seg [C+1] i64 class
+    boundaries; npig [C,4] i32 -> (precision [10,101,C,4,3] f64, recall [10,C,4,3] f64), -1 where a (class, area range) has no ground truth."""
+    _chk(rank, torch.int32, "rank"); _chk(mask, torch.int32, "mask"); _chk(seg, torch.int64, "seg"); _chk(npig, torch.int32, "npig")
+    C, N = int(n_classes), rank.shape[0]
+    if mask.shape != (N, MAP_A) or seg.shape != (C + 1,) or npig.shape != (C, MAP_A):
+        raise ValueError(f"map_accumulate: inconsistent shapes {tuple(rank.shape)} {tuple(mask.shape)} {tuple(seg.shape)} {tuple(npig.shape)} for C={C}")
+    dev = seg.device
+    k = map_constants(dev)
+    precision = torch.empty(MAP_T, MAP_R, C, MAP_A, MAP_M, dtype=torch.float64, device=dev)
+    recall = torch.empty(MAP_T, C, MAP_A, MAP_M, dtype=torch.float64, device=dev)
+    _lib.call("owl_map_accumulate", stream(), rank, mask, seg, npig, k["rec_thr"], k["max_dets"], k["eps"], precision, recall, N, C)
+    return precision, recall
+
+
 _zero_row = {}
 
 
