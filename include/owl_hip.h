@@ -32,9 +32,9 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop).  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd).  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
-#define OWL_ABI_VERSION 7
+#define OWL_ABI_VERSION 8
 const char* owl_last_error(void);
 int owl_abi_version(void);
 
@@ -112,6 +112,13 @@ int owl_merge_ln_fwd(void* stream, const float* x, const void* delta_bf16, float
 int owl_query_normalize(void* stream, const float* queries, float* qhat32, float* qnorm, int64_t nq, int64_t Dt);
 /* sims = max over 3 prompts of (e/(|e|+1e-6)) . qhat (ref src/models.py:25-36); f32 MFMA            */
 int owl_class_sims_fwd(void* stream, const float* e, const float* qhat32, float* sims, unsigned char* argmax, float* inv_norm, int64_t rows, int64_t Dt, int64_t C);
+/* Wide class head (ABI 8): label sets of 1 <= C <= 384 classes; the model takes it for 3C > 32, the entries above keep their 32-prompt limit.
+ * qhat_wide is [nblk][32][Dt] f32 with nblk = ceil(C / 10): class c in block c / 10, its prompts in rows 3 (c % 10) .. + 2, rows 30 / 31 and the
+ * rows of classes >= C zero; qnorm (optional) [32 nblk].  nq = 3 C.                                                                          */
+int owl_query_normalize_wide(void* stream, const float* queries, float* qhat_wide, float* qnorm, int64_t nq, int64_t Dt);
+/* sims [rows, C] f32, argmax [rows, C] u8, inv_norm [rows]: column c carries the bits owl_class_sims_fwd gives for a call on classes
+ * 10 (c / 10) .. + 9 alone.  Dt % 64 == 0                                                                                                   */
+int owl_class_sims_wide_fwd(void* stream, const float* e, const float* qhat_wide, float* sims, unsigned char* argmax, float* inv_norm, int64_t rows, int64_t Dt, int64_t C);
 /* dense2 + box bias + sigmoid + center_to_corners (HF5:998, 1071-1104; ref src/models.py:70-73); D % 8 == 0, D <= 1024 */
 int owl_box_final_fwd(void* stream, const void* h_bf16, const float* w2, const float* b2, const float* box_bias, float* boxes, float* sig_out, int64_t rows, int64_t P, int64_t D);
 
@@ -226,6 +233,12 @@ int owl_merge_ln_bwd(void* stream, const float* dfeats, const float* x, const fl
  * dqhat[32,Dt] = G^T e is then a split-K owl_gemm_nt_bf16, and owl_query_normalize_bwd maps it onto dqueries            */
 int owl_class_sims_bwd(void* stream, const float* dsims, const float* sims, const unsigned char* argmax, const float* inv_norm, const float* e, const float* qhat32, void* de_bf16, void* g_bf16, void* e_bf16, int64_t rows, int64_t Dt, int64_t C);
 int owl_query_normalize_bwd(void* stream, const float* dqhat, const float* queries, float* dqueries, int64_t nq, int64_t Dt);
+/* Wide class head backward (ABI 8).  de (bf16 [rows, Dt]) = inv * (A . qhat_wide) - coef * e as an exact-f32 MFMA product, A the upstream routed to
+ * each class's arg-max prompt; G (bf16 [rows, Qp], Qp = 32 ceil(C / 10) rounded up to a multiple of 256, columns in the wide layout, pad columns
+ * written as zeros) = A * inv; e_bf16 = bf16(e).  dqhat_wide [Qp, Dt] = G^T e_bf16 is a weight-gradient GEMM of the caller's;
+ * owl_query_normalize_wide_bwd ACCUMULATES its image under qhat = Q/|Q| + 1e-6 into dqueries [3C, Dt].  No atomics.  Dt % 32 == 0, Dt <= 1024 */
+int owl_class_sims_wide_bwd(void* stream, const float* dsims, const float* sims, const unsigned char* argmax, const float* inv_norm, const float* e, const float* qhat_wide, void* de_bf16, void* g_bf16, void* e_bf16, int64_t rows, int64_t Dt, int64_t C, int64_t Qp);
+int owl_query_normalize_wide_bwd(void* stream, const float* dqhat_wide, const float* queries, float* dqueries, int64_t nq, int64_t Dt);
 /* dw2 [4,D] and db2 [4] must be contiguous (dw2 then db2); partials = f32 [owl_box_final_bwd_blocks(rows)][5*D+4];
  * du1_colsum (optional, [D]): += column sums of du1 = dense1's bias gradient, from the same pass */
 int owl_box_final_bwd_blocks(int64_t rows);

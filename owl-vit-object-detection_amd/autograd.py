@@ -97,11 +97,12 @@ def _bws(model, B):
     z = ops.zeros_rows
     wide = max(3 * D, I)
     tn_all = all(v % 256 == 0 for v in (D, I, Dt))          # every token-row dW goes through the TN kernel (gemm_tn.hip)
+    Qg = _routed_cols(model)                                 # columns of the routed upstream G = rows of dqhat: 32, or the wide head's Qp
     ws = dict(
-        de=z(Mh, Dt, bf, dev), dqhat=torch.zeros(32, Dt, device=dev), du1=z(Mh, D, bf, dev), du0=z(Mh, D, bf, dev),
-        g32=z(Mh, 32, bf, dev), e_bf=z(Mh, Dt, bf, dev),
+        de=z(Mh, Dt, bf, dev), dqhat=torch.zeros(Qg, Dt, device=dev), du1=z(Mh, D, bf, dev), du0=z(Mh, D, bf, dev),
+        g32=z(Mh, Qg, bf, dev), e_bf=z(Mh, Dt, bf, dev),
         box_part=torch.zeros(_lib.load().owl_box_final_bwd_blocks(Mh), 5 * D + 4, device=dev),
-        slab=torch.zeros(_slab_elems(cfg), device=dev),
+        slab=torch.zeros(_slab_elems(cfg, Qg), device=dev),
         # per-split partial sums of the bias gradients (one row of n_out floats per split of the dW GEMM; at most 256 splits); the class head's chain has its own
         bslab=torch.zeros(256 * max(3 * D, I, Dt), device=dev), bslab2=torch.zeros(256 * max(D, Dt), device=dev),
         dfeats=z(Mh, D, f32, dev), dcls=torch.zeros(B, D, device=dev),
@@ -119,11 +120,11 @@ def _bws(model, B):
         # parity-test configs -- and the 32 x Dt prompt-gradient product)
         tA=None if tn_all else torch.zeros(wide, Mp, dtype=bf, device=dev),
         tB=None if tn_all else torch.zeros(wide, Mp, dtype=bf, device=dev),
-        tAh=torch.zeros(32 if tn_all else max(D, Dt), Mhp, dtype=bf, device=dev),
+        tAh=torch.zeros(32 if tn_all else max(D, Dt, Qg if model.wide_head else 0), Mhp, dtype=bf, device=dev),
         tBh=torch.zeros(max(D, Dt), Mhp, dtype=bf, device=dev),
         wT=torch.zeros(wide * max(D, I), dtype=bf, device=dev),
         # the class head's backward runs beside the box head's on the side stream: its own split-K slab and transposed-weight scratch
-        slab2=torch.zeros(max(_split_k(a, b, 1 << 30) * a * b for a, b in ((Dt, D), (32, Dt))), device=dev),
+        slab2=torch.zeros(max(_split_k(Dt, D, 1 << 30) * Dt * D, _dw_slab_elems(Qg, Dt)), device=dev),
         wT2=torch.zeros(Dt * D, dtype=bf, device=dev),
         tn_all=tn_all,
     )
@@ -139,11 +140,25 @@ def _split_k(n_rows_out, n_cols_out, k):
     return max(1, min(k // 64, slots // tiles))
 
 
-def _slab_elems(cfg):
+def _routed_cols(model):
+    """Columns of the class head's routed upstream G (= rows of dqhat): one 32-column tile, or the wide head's Qp (a multiple of 256)."""
+    return ops.wide_qp(model.cfg.n_classes) if model.wide_head else 32
+
+
+def _dw_slab_elems(n_out, n_in):
+    """f32 elements of the split-K slabs of one dW shape on either route of backward_impl's dW(): the NT kernel's _split_k() splits, or -- a shape
+    the TN kernel takes whole (both sides multiples of 256) -- its DW_ITEMS // tiles splits, which is more for fewer than 512 output rows."""
+    splits = _split_k(n_out, n_in, 1 << 30)
+    if n_out % 256 == 0 and n_in % 256 == 0:
+        splits = max(splits, 256 // ((n_out // 256) * (n_in // 256)))
+    return splits * n_out * n_in
+
+
+def _slab_elems(cfg, routed_cols=32):
     """f32 elements of the split-K slab scratch: max over the dW shapes of splits * n_out * n_in."""
     D, I, Dt = cfg.hidden, cfg.mlp, cfg.text_dim
-    shapes = [(3 * D, D), (D, D), (I, D), (D, I), (Dt, D), (32, Dt)]
-    return max(_split_k(a, b, 1 << 30) * a * b for a, b in shapes)
+    shapes = [(3 * D, D), (D, D), (I, D), (D, I), (Dt, D)]
+    return max(max(_split_k(a, b, 1 << 30) * a * b for a, b in shapes), _dw_slab_elems(routed_cols, Dt))
 
 
 def backward_impl(model, B, d_boxes, d_sims, sims):
@@ -220,9 +235,15 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
     cs, cp, cw = ("slab2", "part2", "wT2") if hs is not main0 else ("slab", "part", "wT")
     # ---- class head ---------------------------------------------------------------------------------
     with torch.cuda.stream(hs):
-        ops.class_sims_bwd(d_sims, sims, ws["argmax"], ws["inv_norm"], ws["e"], ws["qhat"], bw["de"], bw["g32"], bw["e_bf"], Mh, Dt, C)
-        dW(bw["g32"], bw["e_bf"], bw["dqhat"], 32, Dt, Mh, Mhp, None, accumulate=0, part=cp, slab=cs)          # dqhat = G^T e
-        _lib.call("owl_query_normalize_bwd", ops.stream(), bw["dqhat"], P_["queries"], G("queries"), cfg.queries, Dt)
+        if model.wide_head:          # label sets beyond 10 classes: de as a dense f32-MFMA product, G [rows, Qp] in the wide query layout (csrc/class_head_wide.hip)
+            Qp = bw["g32"].shape[1]
+            ops.class_sims_wide_bwd(d_sims, sims, ws["argmax"], ws["inv_norm"], ws["e"], ws["qhat"], bw["de"], bw["g32"], bw["e_bf"], Mh, Dt, C)
+            dW(bw["g32"], bw["e_bf"], bw["dqhat"], Qp, Dt, Mh, Mhp, None, accumulate=0, part=cp, slab=cs)          # dqhat = G^T e
+            ops.query_normalize_wide_bwd(bw["dqhat"], P_["queries"], G("queries"), cfg.queries, Dt)
+        else:
+            ops.class_sims_bwd(d_sims, sims, ws["argmax"], ws["inv_norm"], ws["e"], ws["qhat"], bw["de"], bw["g32"], bw["e_bf"], Mh, Dt, C)
+            dW(bw["g32"], bw["e_bf"], bw["dqhat"], 32, Dt, Mh, Mhp, None, accumulate=0, part=cp, slab=cs)          # dqhat = G^T e
+            _lib.call("owl_query_normalize_bwd", ops.stream(), bw["dqhat"], P_["queries"], G("queries"), cfg.queries, Dt)
         dW(bw["de"], ws["feats"], G("class_predictor.dense0.weight"), Dt, D, Mh, Mhp, G("class_predictor.dense0.bias"), part=cp, slab=cs)
         ops.gemm(ops.EPI_F32, bw["de"], wT("class_predictor.dense0.weight", Dt, D, buf=cw), bw["dfeats"], M=Mh, N=D, K=Dt)
         if hs is not main0:

@@ -8,6 +8,8 @@
 // build) and nothing else -- no kernel stubs, no C++ helpers (tests/test_abi.py).
 #define OWL_API extern "C" __attribute__((visibility("default")))
 
+#define OWL_WIDE_MAX_CLASSES 384   // ceiling of the wide class head (label sets beyond 10 classes): 3 * 384 = 1152 prompts (class_head_wide.hip)
+
 typedef unsigned short bf16_t;  // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;     // MFMA A/B fragment (8 bf16, 4 VGPR)
 typedef __attribute__((ext_vector_type(4))) float f32x4;

@@ -70,6 +70,8 @@ class OwlViT(nn.Module):
         self.device_ = torch.device(device)
         if cfg.head_dim != 64:
             raise ValueError("attention kernels are built for head_dim = 64")
+        if not 1 <= cfg.n_classes <= ops.WIDE_MAX_CLASSES:
+            raise ValueError(f"OwlViT: the class head takes label sets of 1 to {ops.WIDE_MAX_CLASSES} classes (3 prompts each), got {cfg.n_classes}")
         if self.device_.type == "cuda" and torch.cuda.is_available():
             cus = torch.cuda.get_device_properties(self.device_).multi_processor_count
             if cus != ops.CHIP_CUS:
@@ -243,6 +245,11 @@ class OwlViT(nn.Module):
             self._ws[key] = torch.zeros(int(nbytes.item()) // 2, dtype=torch.bfloat16, device=self.device_)
         return self._ws[key]
 
+    @property
+    def wide_head(self) -> bool:
+        """More prompts than one 32-column MFMA tile holds (over 10 classes): the class head runs its wide kernels, forward and backward."""
+        return self.cfg.queries > 32
+
     def _workspace(self, B: int, train: bool = True):
         """Activation workspace of batch size B.  Gradient-recording forwards and no-grad (eval) forwards use SEPARATE sets, so an
         eval forward between a training forward and its backward cannot overwrite what that backward reads; two recording forwards
@@ -256,6 +263,7 @@ class OwlViT(nn.Module):
         M, Mh = B * Tp, B * P
         bf, f32 = torch.bfloat16, torch.float32
         z = ops.zeros_rows
+        nqr = 32 * ops.wide_blocks(C) if self.wide_head else 32
         ws = dict(
             x=z(M, D, f32, dev), x_fin=z(M, D, f32, dev) if train else None, h=z(M, D, bf, dev), qkv=z(M, 3 * D, bf, dev),
             att=z(M, D, bf, dev), g=z(M, I, bf, dev), d1=z(M, D, bf, dev), d2=z(M, D, bf, dev),
@@ -263,7 +271,8 @@ class OwlViT(nn.Module):
             cls_ln=torch.zeros(B, D, device=dev), feats=z(Mh, D, bf, dev), st_post=torch.zeros(M, 2, device=dev),
             st_pp=torch.zeros(Mh, 2, device=dev), hb0=z(Mh, D, bf, dev), ub0=z(Mh, D, bf, dev), hb1=z(Mh, D, bf, dev),
             ub1=z(Mh, D, bf, dev), sig=torch.zeros(Mh, 4, device=dev), e=z(Mh, Dt, f32, dev),
-            qhat=torch.zeros(32, Dt, device=dev), qnorm=torch.zeros(32, device=dev),
+            # query table: [32, Dt] (<= 10 classes: one MFMA tile), or the wide head's [nblk][32][Dt] blocks of 10 classes (csrc/class_head_wide.hip)
+            qhat=torch.zeros(nqr, Dt, device=dev), qnorm=torch.zeros(nqr, device=dev),
             argmax=torch.zeros(Mh, C, dtype=torch.uint8, device=dev), inv_norm=torch.zeros(Mh, device=dev),
             img=torch.zeros(B, 3, cfg.image_size, cfg.image_size, dtype=bf, device=dev),
             gen=0,          # set from the model-global counter by every recording forward (_forward_impl)
@@ -559,8 +568,12 @@ class OwlViT(nn.Module):
         # ---- class head (ref src/models.py:24-38) ------------------------------------------------------
         with torch.cuda.stream(side if side is not None else main):
             ops.gemm(ops.EPI_F32, feats, tv("class_predictor.dense0.weight"), ws["e"], bias=P_["class_predictor.dense0.bias"], M=Mh, N=Dt, K=D)
-            ops.query_normalize(P_["queries"], ws["qhat"], ws["qnorm"], cfg.queries, Dt)
-            ops.class_sims(ws["e"], ws["qhat"], pred_sims, ws["argmax"], ws["inv_norm"], Mh, Dt, C)
+            if self.wide_head:          # label sets beyond 10 classes: the query blocks of csrc/class_head_wide.hip
+                ops.query_normalize_wide(P_["queries"], ws["qhat"], ws["qnorm"], cfg.queries, Dt)
+                ops.class_sims_wide(ws["e"], ws["qhat"], pred_sims, ws["argmax"], ws["inv_norm"], Mh, Dt, C)
+            else:
+                ops.query_normalize(P_["queries"], ws["qhat"], ws["qnorm"], cfg.queries, Dt)
+                ops.class_sims(ws["e"], ws["qhat"], pred_sims, ws["argmax"], ws["inv_norm"], Mh, Dt, C)
         # ---- box head (HF5:983-999) + bias / sigmoid / corners ---------------------------------------
         ops.gemm(ops.EPI_GELU_BF16, feats, tv("box_head.dense0.weight"), ws["hb0"], bias=P_["box_head.dense0.bias"],
                  aux=ws["ub0"] if save else None, M=Mh, N=D, K=D)

@@ -149,6 +149,33 @@ def class_sims(e, qhat32, sims, argmax, inv_norm, rows, Dt, C):
     _lib.call("owl_class_sims_fwd", stream(), e, qhat32, sims, argmax, inv_norm, rows, Dt, C)
 
 
+WIDE_MAX_CLASSES = 384     # ceiling of the wide class head (csrc/common.h OWL_WIDE_MAX_CLASSES)
+
+
+def wide_blocks(C: int) -> int:
+    """Query blocks (10 classes = 30 prompts in a 32-row MFMA tile) of the wide class head's [nblk][32][Dt] layout."""
+    return (int(C) + 9) // 10
+
+
+def wide_qp(C: int) -> int:
+    """Columns of the wide class head's routed upstream G [rows, Qp]: 32 per query block, rounded up to the TN weight-gradient kernel's 256."""
+    return (32 * wide_blocks(C) + 255) // 256 * 256
+
+
+def query_normalize_wide(queries, qhat_wide, qnorm, nq, Dt):
+    _chk(queries, torch.float32, "queries"); _chk(qhat_wide, torch.float32, "qhat_wide")
+    if qhat_wide.numel() < 32 * wide_blocks(nq // 3) * Dt:
+        raise ValueError("query_normalize_wide: qhat_wide must hold [ceil(C / 10) * 32, Dt] floats")
+    _lib.call("owl_query_normalize_wide", stream(), queries, qhat_wide, qnorm, nq, Dt)
+
+
+def class_sims_wide(e, qhat_wide, sims, argmax, inv_norm, rows, Dt, C):
+    _chk(e, torch.float32, "e"); _chk(qhat_wide, torch.float32, "qhat_wide")
+    if qhat_wide.numel() < 32 * wide_blocks(C) * Dt:
+        raise ValueError("class_sims_wide: qhat_wide must hold [ceil(C / 10) * 32, Dt] floats")
+    _lib.call("owl_class_sims_wide_fwd", stream(), e, qhat_wide, sims, argmax, inv_norm, rows, Dt, C)
+
+
 def box_final(h, w2, b2, box_bias, boxes, sig, rows, P, D):
     _chk(h, torch.bfloat16, "h"); _chk(w2, torch.float32, "w2")
     _lib.call("owl_box_final_fwd", stream(), h, w2, b2, box_bias, boxes, sig, rows, P, D)
@@ -210,6 +237,22 @@ def merge_ln_bwd(dfeats, x, cls_ln, st1, st2, g1, b1, g2, dx, dcls_ws, dg1, db1,
 
 def class_sims_bwd(dsims, sims, argmax, inv_norm, e, qhat32, de, g32, e_bf16, rows, Dt, C):
     _lib.call("owl_class_sims_bwd", stream(), dsims, sims, argmax, inv_norm, e, qhat32, de, g32, e_bf16, rows, Dt, C)
+
+
+def class_sims_wide_bwd(dsims, sims, argmax, inv_norm, e, qhat_wide, de, g, e_bf16, rows, Dt, C):
+    """g: bf16 [>= rows, wide_qp(C)] (every element of the first `rows` rows is written)."""
+    _chk(g, torch.bfloat16, "g"); _chk(de, torch.bfloat16, "de"); _chk(e_bf16, torch.bfloat16, "e_bf16")
+    Qp = wide_qp(C)
+    if g.shape[-1] != Qp or g.numel() < rows * Qp or de.numel() < rows * Dt or e_bf16.numel() < rows * Dt:
+        raise ValueError(f"class_sims_wide_bwd: g must be [rows, {Qp}], de / e_bf16 [rows, Dt]")
+    _lib.call("owl_class_sims_wide_bwd", stream(), dsims, sims, argmax, inv_norm, e, qhat_wide, de, g, e_bf16, rows, Dt, C, Qp)
+
+
+def query_normalize_wide_bwd(dqhat_wide, queries, dqueries, nq, Dt):
+    _chk(dqhat_wide, torch.float32, "dqhat_wide"); _chk(queries, torch.float32, "queries"); _chk(dqueries, torch.float32, "dqueries")
+    if dqhat_wide.numel() < 32 * wide_blocks(nq // 3) * Dt:
+        raise ValueError("query_normalize_wide_bwd: dqhat_wide must hold [ceil(C / 10) * 32, Dt] floats")
+    _lib.call("owl_query_normalize_wide_bwd", stream(), dqhat_wide, queries, dqueries, nq, Dt)
 
 
 def box_final_bwd(dboxes, sig, h1, u1, w2, du1, partials, dw2_db2, rows, D, du1_colsum=None):
