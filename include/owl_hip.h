@@ -32,7 +32,7 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd).  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays.  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
 #define OWL_ABI_VERSION 8
 const char* owl_last_error(void);
@@ -250,6 +250,22 @@ int owl_colsum_f32(void* stream, const float* in, float* colsum, int64_t R, int6
  * decoupled weight decay, bias-corrected; g is pre-scaled by grad_scale (1/world after the sum all-reduce);
  * optionally refreshes the bf16 compute copy in the same pass                                              */
 int owl_adamw_step(void* stream, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale);
+
+/* ---- global gradient-norm clipping + parameter groups for the step above (torch.nn.utils.clip_grad_norm_, L2, + torch.optim.AdamW with several
+ * param groups), in two launches on `stream`:
+ *   owl_grad_sumsq          one read of g: an f64 sum of squares per workgroup into `workspace` (owl_grad_norm_workspace_bytes(n); HOST pointer
+ *                           `bytes`).  The grid depends on n alone and every sum runs in a fixed order (no atomics): the same g gives the same bits.
+ *   owl_adamw_step_grouped  owl_adamw_step with lr / weight_decay per SEGMENT of the bucket: seg_end / seg_lr / seg_wd are HOST arrays of nseg entries
+ *                           (1 <= nseg <= 32), read by this call and passed to the kernel by value; seg_end[s] = exclusive end offset of segment s in
+ *                           elements, multiples of 4, strictly increasing, seg_end[nseg-1] == n.  A null seg_lr / seg_wd means the scalar `lr` /
+ *                           `weight_decay` for every segment.  max_norm > 0: every workgroup adds the partials of owl_grad_sumsq(g) in one fixed order,
+ *                           norm = sqrt(sum) * |grad_scale| (the norm of the SCALED gradient), coef = min(1, max_norm / (norm + 1e-6)), the step uses
+ *                           g * grad_scale * coef, and *norm_out (DEVICE f32) receives norm -- read it whenever a sync is acceptable.  max_norm <= 0:
+ *                           no clipping; workspace and norm_out are neither read nor written (may be null) and coef is exactly 1.
+ * One segment over everything without clipping gives the bits of owl_adamw_step.                                                                 */
+int owl_grad_norm_workspace_bytes(int64_t n, int64_t* bytes);
+int owl_grad_sumsq(void* stream, const float* g, int64_t n, void* workspace);
+int owl_adamw_step_grouped(void* stream, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale, const int64_t* seg_end, const float* seg_lr, const float* seg_wd, int nseg, float max_norm, const void* workspace, float* norm_out);
 
 /* ---- utilities ------------------------------------------------------------------------------------ */
 int owl_cast_f32_bf16(void* stream, const float* in, void* out, int64_t n);
