@@ -20,12 +20,18 @@ Two schedules:
     (logging a gradient norm from `p.grad`, cloning `flat_param`) must call `finish()` first -- and reads zeros from the gradients
     afterwards (inspect them with the in-line schedule).
 The same code runs on CPU tensors with the gloo backend (tests/test_ddp_cpu.py; in-line schedule).
+
+The eval half: `eval_indices` / `EvalSampler` give each rank the images `rank, rank + world, ...` of the test set, unpadded, and
+`all_gather_ragged` is the collective `metrics.MeanAveragePrecision.compute()` merges the ranks' records with (per-rank row counts first, then
+one padded gather of the rows as bytes).
 """
+import math
 import os
 import socket
 
 import torch
 import torch.distributed as dist
+import torch.utils.data
 
 
 def _free_port() -> int:
@@ -75,6 +81,81 @@ def broadcast_flat(flat_param: torch.Tensor, src: int = 0, group=None) -> torch.
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
         dist.broadcast(flat_param, src=src, group=group)
     return flat_param
+
+
+def _shard(rank=None, world=None, group=None):
+    """(rank, world) of this process in `group`: the arguments where given, else torch.distributed's, else (0, 1)."""
+    live = dist.is_available() and dist.is_initialized()
+    rank = (dist.get_rank(group) if live else 0) if rank is None else int(rank)
+    world = (dist.get_world_size(group) if live else 1) if world is None else int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"shard ({rank}, {world}): need 0 <= rank < world")
+    return rank, world
+
+
+def eval_indices(n: int, rank: int = None, world: int = None) -> range:
+    """The shard of an n-image eval set: range(rank, n, world).  No padding, no shuffle; the shards partition range(n) and differ by at most one
+    image.  Position i of the shard is image i * world + rank: the default image key of `metrics.MeanAveragePrecision`."""
+    rank, world = _shard(rank, world)
+    return range(rank, int(n), world)
+
+
+class EvalSampler(torch.utils.data.Sampler):
+    """`eval_indices` as the sampler of the test DataLoader (`DataLoader(test_set, batch_size=..., sampler=EvalSampler(test_set))`).
+
+    `DistributedSampler` is the wrong tool for evaluation: it pads the shards to equal length by REPEATING images, so the data set's metric
+    would count some images twice -- `MeanAveragePrecision.compute()` refuses that (duplicate image keys raise).  Here the last ranks simply
+    hold one image less; the merge in `compute()` is ragged."""
+
+    def __init__(self, dataset_or_len, group=None):
+        self.n = int(dataset_or_len) if isinstance(dataset_or_len, int) else len(dataset_or_len)
+        self.rank, self.world = _shard(group=group)
+
+    def __iter__(self):
+        return iter(range(self.rank, self.n, self.world))
+
+    def __len__(self):
+        return len(range(self.rank, self.n, self.world))
+
+
+def collective_device(device, group=None) -> torch.device:
+    """Where a tensor on `device` has to live to go through `group`'s backend: RCCL ("nccl") takes device tensors as they are, any other backend
+    (gloo) is handed host copies."""
+    device = torch.device(device)
+    return device if "nccl" in str(dist.get_backend(group)) else torch.device("cpu")
+
+
+def all_gather_ragged(tensors, group=None):
+    """Every rank holds `tensors`: a list of tensors of any dtypes and trailing shapes that share their first dimension n (n differs between ranks,
+    0 included).  -> (the list of the same tensors concatenated over the ranks in rank order, the per-rank counts [world] as a list).
+
+    The counts are exchanged first; the rows are then packed as bytes, padded to the largest count and gathered in ONE collective, and the padding
+    is cut by count (no sentinel).  Host tensors and device tensors both work; device tensors go through host memory unless the backend is RCCL.
+    The collectives are issued in the current stream's order.  Every rank of the group must call this (it synchronises: the counts are read back)."""
+    tensors = [t.contiguous() for t in tensors]
+    n, dev = tensors[0].shape[0], tensors[0].device
+    if any(t.shape[0] != n or t.device != dev for t in tensors):
+        raise ValueError("all_gather_ragged: the tensors must share their first dimension and their device")
+    world = dist.get_world_size(group)
+    via = collective_device(dev, group)
+    counts = [torch.zeros(1, dtype=torch.int64, device=via) for _ in range(world)]
+    dist.all_gather(counts, torch.full((1,), n, dtype=torch.int64, device=via), group=group)
+    counts = [int(c) for c in torch.cat(counts).tolist()]
+    top = max(counts)
+    if top == 0:
+        return [t[:0].clone() for t in tensors], counts
+    widths = [t.element_size() * math.prod(t.shape[1:]) for t in tensors]          # bytes per row
+    rows = torch.zeros(top, sum(widths), dtype=torch.uint8, device=via)
+    if n:
+        rows[:n] = torch.cat([t.view(torch.uint8).reshape(n, w) for t, w in zip(tensors, widths)], dim=1).to(via)
+    parts = [torch.empty_like(rows) for _ in range(world)]
+    dist.all_gather(parts, rows, group=group)
+    rows = torch.cat([p[:c] for p, c in zip(parts, counts)]).to(dev)
+    out, at = [], 0
+    for t, w in zip(tensors, widths):
+        out.append(rows[:, at:at + w].contiguous().view(t.dtype).reshape((rows.shape[0],) + tuple(t.shape[1:])))
+        at += w
+    return out, counts
 
 
 class DataParallel:

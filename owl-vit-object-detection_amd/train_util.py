@@ -5,7 +5,7 @@
 (boxes [B,n,4], metadata values scalars or [B]).  Host-side elementwise glue on a few dozen numbers per
 image (the reference runs it on the CPU before `.to(device)`, main.py:79) -- not a kernel.
 
-`update_metrics(metric, metadata, pred_boxes, pred_classes, scores, boxes, labels)` (ref src/train_util.py:37-64, called at main.py:120-128):
+`update_metrics(metric, metadata, pred_boxes, pred_classes, scores, boxes, labels, image_ids=None)` (ref src/train_util.py:37-64, called at main.py:120-128):
 hands one post-processed batch to the mAP metric.  With `metrics.MeanAveragePrecision` the normalised boxes go to the device kernel as they are
 (the scaling to pixels is the kernel's f32 multiply): no `.cpu()` / `.cuda()` hops, no host synchronisation, and the caller's tensors are not
 scaled in place (the reference's are).  `reverse_labelmap` / `labels_to_classnames`: the labelmap helpers of ref src/train_util.py:26-34.
@@ -66,14 +66,17 @@ def labels_to_classnames(labels, labelmap):
     return [[labelmap[str(int(l))] for l in labels[0].tolist() if int(l) >= 0]]
 
 
-def update_metrics(metric, metadata, pred_boxes, pred_classes, scores, boxes, labels):
-    """pred_boxes [B,K,4] / boxes [B,n,4]: normalised xyxy; pred_classes [B,K], labels [B,n] (-1 = padding); metadata["width"], ["height"]: number or [B]."""
+def update_metrics(metric, metadata, pred_boxes, pred_classes, scores, boxes, labels, image_ids=None):
+    """pred_boxes [B,K,4] / boxes [B,n,4]: normalised xyxy; pred_classes [B,K], labels [B,n] (-1 = padding); metadata["width"], ["height"]: number or [B];
+    image_ids: None or [B] image keys for `metrics.MeanAveragePrecision` (see there; any other metric takes none)."""
     width, height = metadata["width"], metadata["height"]
     if hasattr(metric, "update_batched"):
         dev = pred_boxes.device
         metric.update_batched(pred_boxes, pred_classes, scores, None, boxes.to(dev, non_blocking=True), labels.to(dev, non_blocking=True), None,
-                              width=width, height=height)
+                              width=width, height=height, image_ids=image_ids)
         return
+    if image_ids is not None:
+        raise ValueError("update_metrics: image_ids are for metrics.MeanAveragePrecision (this metric has no update_batched)")
     # any other metric with torchmetrics' interface: per-image dicts of pixel boxes, scaled out of place on the device the predictions are on
     dev = pred_boxes.device
     pred_px = scale_bounding_box(pred_boxes, width, height, mode="up")
