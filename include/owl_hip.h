@@ -32,7 +32,7 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays.  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings).  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
 #define OWL_ABI_VERSION 8
 const char* owl_last_error(void);
@@ -245,6 +245,18 @@ int owl_box_final_bwd_blocks(int64_t rows);
 int owl_box_final_bwd(void* stream, const float* dboxes, const float* sig, const void* h1_bf16, const void* u1_bf16, const float* w2, void* du1_bf16, float* partials, float* dw2_db2, int64_t rows, int64_t D, float* du1_colsum);
 int owl_transpose_colsum_bf16(void* stream, const void* in, int64_t ld_in, void* out_t, int64_t ld_out, float* colsum, int64_t R, int64_t C, float* partials, int64_t partials_floats);
 int owl_colsum_f32(void* stream, const float* in, float* colsum, int64_t R, int64_t C, float* partials, int64_t partials_floats);
+/* Backward below encoder layer 0 (HF5:282-288, 336-343), run only when backbone.embeddings is trainable (still ABI 8: additive).
+ * owl_embed_bwd: dx f32 [B, Tp, D] = d(output of the embeddings) -> dpos [T, D] += sum_b dx[b, t, :], dcls [D] += sum_b dx[b, 0, :], and
+ * dE bf16 [B (T - 1), D] = the patch rows of dx packed without the class and pad rows (the dY operand of the patch-embedding weight gradient).  One launch;
+ * the sum over b runs in index order inside one thread: no atomics, bitwise reproducible.  D % 8 == 0; dpos, dcls, dE 16-byte aligned.
+ * owl_im2row_bf16: image bf16 [B, 3, S, S] -> out bf16 [B (S / ps)^2, ld_out], column (c ps + i) ps + j = pixel (c, gy ps + i, gx ps + j): the conv weight's
+ * own [D, 3, ps, ps] column order (NOT the gather order of owl_patch_embed_bf16), the X operand of that weight gradient.  ld_out >= 3 ps^2, ld_out % 8 == 0;
+ * columns [3 ps^2, ld_out) are not written.  ps even.                                                                                                    */
+int owl_embed_bwd(void* stream, const float* dx, float* dpos, float* dcls, void* dE_bf16, int64_t B, int64_t T, int64_t Tp, int64_t D);
+int owl_im2row_bf16(void* stream, const void* image_bf16, void* out_bf16, int64_t ld_out, int64_t B, int64_t S, int64_t ps);
+/* owl_slab_reduce for slabs with pad columns: out [rows, cols] (+)= sum_s slabs[s * slab_stride + r * ld_slab + c], splits added in index order.  For a split-K
+ * weight gradient whose inner size is no multiple of 8 (owl_gemm_nt_bf16 needs N % 8 == 0: the 588 columns of L/14's patch embedding run as 592).  cols, ld_slab % 4 == 0 */
+int owl_slab_reduce_rows(void* stream, const float* slabs, float* out, int64_t rows, int64_t cols, int64_t ld_slab, int64_t slab_stride, int nsplit, int accumulate);
 
 /* ---- fused AdamW on the flat trainable bucket (replaces torch.optim.AdamW.step, ref main.py:56-60,91) -----
  * decoupled weight decay, bias-corrected; g is pre-scaled by grad_scale (1/world after the sum all-reduce);

@@ -1,9 +1,10 @@
 """The autograd edge of the HIP train path: ONE coarse torch.autograd.Function around the whole vision
-model.  forward = OwlViT._forward_impl (saving the trainable layer's activations); backward = a fixed
-sequence of hand-written HIP kernels (csrc/backward.hip, attention_bwd.hip, gemm.hip) for exactly the
-trainable set of the reference freeze rule (ref src/models.py:173-184): queries, encoder layer 11,
-post_layernorm, post_post_layernorm, class_predictor.dense0, box_head.  Everything upstream of the
-trainable layer is frozen, so the backward stops there (ref main.py:90).
+model.  forward = OwlViT._forward_impl (saving the activations of the layers the backward crosses); backward = a
+sequence of hand-written HIP kernels (csrc/backward.hip, attention_bwd.hip, gemm.hip) laid out at construction for the
+model's trainable set -- by default that of the reference freeze rule (ref src/models.py:173-184): queries, encoder
+layer 11, post_layernorm, post_post_layernorm, class_predictor.dense0, box_head.  The dX chain walks from the heads down
+to the model's `backward_floor` and stops there (ref main.py:90): an encoder layer on the way is either trained (dX + dW)
+or crossed (dX only); below layer 0 lie pre_layernorm and the embeddings.
 
 Parameter gradients are ACCUMULATED by the kernels directly into `model.flat_grad` (each parameter's
 .grad is a view of that bucket), so `loss.backward()` leaves one contiguous buffer ready for the single
@@ -98,11 +99,14 @@ def _bws(model, B):
     wide = max(3 * D, I)
     tn_all = all(v % 256 == 0 for v in (D, I, Dt))          # every token-row dW goes through the TN kernel (gemm_tn.hip)
     Qg = _routed_cols(model)                                 # columns of the routed upstream G = rows of dqhat: 32, or the wide head's Qp
+    Kpe = cfg.patch_k if model._train_emb else 0             # trainable embeddings: the patch-embedding weight gradient [D, 3 p p] shares the head-row scratch
+    pe_nt = Kpe and not (Kpe % 256 == 0 and D % 256 == 0)    # ... on the transposes + NT split-K route
     ws = dict(
         de=z(Mh, Dt, bf, dev), dqhat=torch.zeros(Qg, Dt, device=dev), du1=z(Mh, D, bf, dev), du0=z(Mh, D, bf, dev),
         g32=z(Mh, Qg, bf, dev), e_bf=z(Mh, Dt, bf, dev),
         box_part=torch.zeros(_lib.load().owl_box_final_bwd_blocks(Mh), 5 * D + 4, device=dev),
-        slab=torch.zeros(_slab_elems(cfg, Qg), device=dev),
+        slab=torch.zeros(max(_slab_elems(cfg, Qg), _dw_slab_elems(D, (Kpe + 7) // 8 * 8) if Kpe else 0), device=dev),
+        sink=torch.zeros(4 * D + 8, device=dev),          # where kernels that must run leave the gradients of FROZEN tensors (never read; not in the bucket)
         # per-split partial sums of the bias gradients (one row of n_out floats per split of the dW GEMM; at most 256 splits); the class head's chain has its own
         bslab=torch.zeros(256 * max(3 * D, I, Dt), device=dev), bslab2=torch.zeros(256 * max(D, Dt), device=dev),
         dfeats=z(Mh, D, f32, dev), dcls=torch.zeros(B, D, device=dev),
@@ -120,8 +124,8 @@ def _bws(model, B):
         # parity-test configs -- and the 32 x Dt prompt-gradient product)
         tA=None if tn_all else torch.zeros(wide, Mp, dtype=bf, device=dev),
         tB=None if tn_all else torch.zeros(wide, Mp, dtype=bf, device=dev),
-        tAh=torch.zeros(32 if tn_all else max(D, Dt, Qg if model.wide_head else 0), Mhp, dtype=bf, device=dev),
-        tBh=torch.zeros(max(D, Dt), Mhp, dtype=bf, device=dev),
+        tAh=torch.zeros(max(32 if tn_all else max(D, Dt, Qg if model.wide_head else 0), D if pe_nt else 0), Mhp, dtype=bf, device=dev),
+        tBh=torch.zeros(max(D, Dt, Kpe if pe_nt else 0), Mhp, dtype=bf, device=dev),
         wT=torch.zeros(wide * max(D, I), dtype=bf, device=dev),
         # the class head's backward runs beside the box head's on the side stream: its own split-K slab and transposed-weight scratch
         slab2=torch.zeros(max(_split_k(Dt, D, 1 << 30) * Dt * D, _dw_slab_elems(Qg, Dt)), device=dev),
@@ -161,6 +165,39 @@ def _slab_elems(cfg, routed_cols=32):
     return max(max(_split_k(a, b, 1 << 30) * a * b for a, b in shapes), _dw_slab_elems(routed_cols, Dt))
 
 
+def patch_weight_grad(dE, patches, grad_w, D, K, rows, scratch=None, accumulate=1):
+    """grad_w [D, K] (+)= dE[rows, D]^T patches[rows, K] -- the patch-embedding weight gradient, on the routes of backward_impl's dW(): the TN kernel where
+    both sides are multiples of 256, transposes + NT split-K otherwise (K no multiple of 8, L/14's 588: the product runs 8-padded and the slabs are reduced
+    row by row).  dE [>= rows, D] and patches [>= rows, ld >= K] bf16; scratch: dict(slab, tA [>= D, pad_rows(rows)], tB [>= K, pad_rows(rows)]) with the pad
+    columns [rows, pad_rows(rows)) of tA / tB zero (default: allocated here)."""
+    rows_pad = ops.pad_rows(rows)
+    Kp = (K + 7) // 8 * 8
+    tn = K % 256 == 0 and D % 256 == 0
+    if scratch is None:
+        dev = dE.device
+        scratch = dict(slab=torch.zeros(_dw_slab_elems(D, Kp), device=dev),
+                       tA=None if tn else torch.zeros(D, rows_pad, dtype=torch.bfloat16, device=dev), tB=None if tn else torch.zeros(K, rows_pad, dtype=torch.bfloat16, device=dev))
+    slab = scratch["slab"]
+    if tn:
+        tiles = (D // 256) * (K // 256)
+        ns = ops.gemm_tn_slab(dE, patches, slab, rows, D, K, max(1, min(DW_ITEMS, 256) // tiles))
+        _lib.call("owl_slab_reduce", ops.stream(), slab, grad_w, D * K, D * K, ns, accumulate)
+        return
+    tA, tB = scratch["tA"], scratch["tB"]
+    ld = tA.shape[1]
+    assert ld == rows_pad and tB.shape[1] == rows_pad and tA.shape[0] >= D and tB.shape[0] >= K
+    ops.transpose_colsum(dE, tA, None, rows, D, ld_in=dE.shape[-1], ld_out=ld)
+    ops.transpose_colsum(patches, tB, None, rows, K, ld_in=patches.shape[-1], ld_out=ld)
+    want = _split_k(D, Kp, rows_pad)
+    ns = _lib.load().owl_gemm_effective_splits(rows_pad, want)
+    # (rows [K, Kp) of the W operand do not exist: w_rows clamps the loads, and the reducer below leaves those columns of the slabs alone)
+    ops.gemm(ops.EPI_SLAB_F32, tA, tB, slab, M=D, N=Kp, K=rows_pad, lda=ld, ldw=ld, ldo=Kp, a_rows=D, w_rows=K, splits=want)
+    if Kp == K:
+        _lib.call("owl_slab_reduce", ops.stream(), slab, grad_w, D * K, D * K, ns, accumulate)
+    else:
+        _lib.call("owl_slab_reduce_rows", ops.stream(), slab, grad_w, D, K, Kp, D * Kp, ns, accumulate)
+
+
 def backward_impl(model, B, d_boxes, d_sims, sims):
     cfg = model.cfg
     D, I, H, Tp, T, P, Dt, C = cfg.hidden, cfg.mlp, cfg.heads, cfg.tokens_padded, cfg.tokens, cfg.patches, cfg.text_dim, cfg.n_classes
@@ -173,7 +210,11 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
     _attach_grads(model)
     G = lambda n: P_[n].grad                      # views into model.flat_grad (accumulated into)
     tv = model._tview
-    tl = f"backbone.encoder.layers.{cfg.trainable_layer()}."
+    units, tls, floor, low = model._units, model._tl_set, model.backward_floor, model._chain_low
+    t_q, t_cls, t_box = "queries" in units, "class_predictor.dense0" in units, "box_head" in units
+    below_heads = floor != "heads"                # the dX chain goes on below feats
+    below_enc = floor in ("pre_layernorm", "embeddings")
+    LP = lambda i: f"backbone.encoder.layers.{i}."
     d_boxes = d_boxes.contiguous().float()
     d_sims = d_sims.contiguous().float()
 
@@ -183,7 +224,10 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
         torch.cuda.current_stream().wait_event(model._wt_event)
 
     def wT(name, rows, cols, buf="wT"):
-        """bf16 transpose of a trainable weight [rows, cols] -> [cols, rows]: the forward's pre-transposed copy, or (pretranspose off) made here in scratch."""
+        """bf16 transpose of a weight [rows, cols] -> [cols, rows].  Trainable: the forward's pre-transposed copy, or (pretranspose off) made here in scratch;
+        frozen but crossed by the dX chain: the static copy made at construction."""
+        if name not in model.flat_offsets:
+            return model._fz[name + ".T"]
         if pre_wt is not None:
             return pre_wt[name]
         out = bw[buf][: rows * cols].view(cols, rows)
@@ -225,6 +269,8 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
     # two contributions: same bits.
     # (streams: in-line, the backward shares the forward's side streams; as a deferred tail -- models.OwlViT.overlap_tail -- it has side streams
     #  and fork / join events of its own, because the next forward is using the model's while this runs)
+    # A frozen head unit launches no dW; where the dX chain stops at the heads (floor "heads") nothing below e / feats runs for it either, and a head
+    # that neither trains nor is crossed does not run at all.
     S, J, fork = model._bwd_streams()
     main0 = torch.cuda.current_stream()
     hs = S(1) if (model.head_streams and model.encoder_streams > 1 and len(model._encoder_chunks(B)) > 1 and bw["tn_all"]) else main0
@@ -235,44 +281,66 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
     cs, cp, cw = ("slab2", "part2", "wT2") if hs is not main0 else ("slab", "part", "wT")
     # ---- class head ---------------------------------------------------------------------------------
     with torch.cuda.stream(hs):
-        if model.wide_head:          # label sets beyond 10 classes: de as a dense f32-MFMA product, G [rows, Qp] in the wide query layout (csrc/class_head_wide.hip)
-            Qp = bw["g32"].shape[1]
-            ops.class_sims_wide_bwd(d_sims, sims, ws["argmax"], ws["inv_norm"], ws["e"], ws["qhat"], bw["de"], bw["g32"], bw["e_bf"], Mh, Dt, C)
-            dW(bw["g32"], bw["e_bf"], bw["dqhat"], Qp, Dt, Mh, Mhp, None, accumulate=0, part=cp, slab=cs)          # dqhat = G^T e
-            ops.query_normalize_wide_bwd(bw["dqhat"], P_["queries"], G("queries"), cfg.queries, Dt)
-        else:
-            ops.class_sims_bwd(d_sims, sims, ws["argmax"], ws["inv_norm"], ws["e"], ws["qhat"], bw["de"], bw["g32"], bw["e_bf"], Mh, Dt, C)
-            dW(bw["g32"], bw["e_bf"], bw["dqhat"], 32, Dt, Mh, Mhp, None, accumulate=0, part=cp, slab=cs)          # dqhat = G^T e
-            _lib.call("owl_query_normalize_bwd", ops.stream(), bw["dqhat"], P_["queries"], G("queries"), cfg.queries, Dt)
-        dW(bw["de"], ws["feats"], G("class_predictor.dense0.weight"), Dt, D, Mh, Mhp, G("class_predictor.dense0.bias"), part=cp, slab=cs)
-        ops.gemm(ops.EPI_F32, bw["de"], wT("class_predictor.dense0.weight", Dt, D, buf=cw), bw["dfeats"], M=Mh, N=D, K=Dt)
+        if t_q or t_cls or below_heads:
+            if model.wide_head:          # label sets beyond 10 classes: de as a dense f32-MFMA product, G [rows, Qp] in the wide query layout (csrc/class_head_wide.hip)
+                Qp = bw["g32"].shape[1]
+                ops.class_sims_wide_bwd(d_sims, sims, ws["argmax"], ws["inv_norm"], ws["e"], ws["qhat"], bw["de"], bw["g32"], bw["e_bf"], Mh, Dt, C)
+                if t_q:
+                    dW(bw["g32"], bw["e_bf"], bw["dqhat"], Qp, Dt, Mh, Mhp, None, accumulate=0, part=cp, slab=cs)          # dqhat = G^T e
+                    ops.query_normalize_wide_bwd(bw["dqhat"], P_["queries"], G("queries"), cfg.queries, Dt)
+            else:
+                ops.class_sims_bwd(d_sims, sims, ws["argmax"], ws["inv_norm"], ws["e"], ws["qhat"], bw["de"], bw["g32"], bw["e_bf"], Mh, Dt, C)
+                if t_q:
+                    dW(bw["g32"], bw["e_bf"], bw["dqhat"], 32, Dt, Mh, Mhp, None, accumulate=0, part=cp, slab=cs)          # dqhat = G^T e
+                    _lib.call("owl_query_normalize_bwd", ops.stream(), bw["dqhat"], P_["queries"], G("queries"), cfg.queries, Dt)
+            if t_cls:
+                dW(bw["de"], ws["feats"], G("class_predictor.dense0.weight"), Dt, D, Mh, Mhp, G("class_predictor.dense0.bias"), part=cp, slab=cs)
+            if below_heads:
+                ops.gemm(ops.EPI_F32, bw["de"], wT("class_predictor.dense0.weight", Dt, D, buf=cw), bw["dfeats"], M=Mh, N=D, K=Dt)
         if hs is not main0:
             ev_h[1].record(hs)
     # ---- box head -------------------------------------------------------------------------------------
-    gw2, gb2 = G("box_head.dense2.weight"), G("box_head.dense2.bias")
-    assert gb2.data_ptr() == gw2.data_ptr() + 4 * gw2.numel(), "dense2 weight/bias grads must be adjacent in the flat bucket"
-    ops.box_final_bwd(d_boxes, ws["sig"], ws["hb1"], ws["ub1"], P_["box_head.dense2.weight"], bw["du1"], bw["box_part"], gw2, Mh, D,
-                      du1_colsum=G("box_head.dense1.bias"))          # (dense1's bias gradient from the same pass: no column-sum launch over du1)
-    dW(bw["du1"], ws["hb0"], G("box_head.dense1.weight"), D, D, Mh, Mhp, None)
-    ops.gemm(ops.EPI_DGELU_BF16, bw["du1"], wT("box_head.dense1.weight", D, D), bw["du0"], aux=ws["ub0"], M=Mh, N=D, K=D)
-    dW(bw["du0"], ws["feats"], G("box_head.dense0.weight"), D, D, Mh, Mhp, G("box_head.dense0.bias"))
-    w0T = wT("box_head.dense0.weight", D, D)
+    w0T = None
+    if t_box or below_heads:
+        if t_box:
+            gw2, gb2 = G("box_head.dense2.weight"), G("box_head.dense2.bias")
+            assert gb2.data_ptr() == gw2.data_ptr() + 4 * gw2.numel(), "dense2 weight/bias grads must be adjacent in the flat bucket"
+        else:
+            gw2 = bw["sink"]          # (the kernel has to run for du1 and takes no null there)
+        ops.box_final_bwd(d_boxes, ws["sig"], ws["hb1"], ws["ub1"], P_["box_head.dense2.weight"], bw["du1"], bw["box_part"], gw2, Mh, D,
+                          du1_colsum=G("box_head.dense1.bias") if t_box else None)          # (dense1's bias gradient from the same pass: no column-sum launch over du1)
+        if t_box:
+            dW(bw["du1"], ws["hb0"], G("box_head.dense1.weight"), D, D, Mh, Mhp, None)
+        ops.gemm(ops.EPI_DGELU_BF16, bw["du1"], wT("box_head.dense1.weight", D, D), bw["du0"], aux=ws["ub0"], M=Mh, N=D, K=D)
+        if t_box:
+            dW(bw["du0"], ws["feats"], G("box_head.dense0.weight"), D, D, Mh, Mhp, G("box_head.dense0.bias"))
+        if below_heads:
+            w0T = wT("box_head.dense0.weight", D, D)
     if hs is not main0:
         main0.wait_event(ev_h[1])                 # d(feats) of the class head is in place (and the side stream's scratch is free again)
+    if not below_heads:
+        return
     ops.gemm(ops.EPI_ACC_F32, bw["du0"], w0T, bw["dfeats"], M=Mh, N=D, K=D)
     # ---- merge + the two final LayerNorms --------------------------------------------------------------
+    # (the kernel takes no null for the four affine gradients: those of a frozen LayerNorm go to the sink)
+    sink = bw["sink"]
+    t_pl, t_ppl = "backbone.post_layernorm" in units, "post_post_layernorm" in units
+    last = cfg.layers - 1
     ops.merge_ln_bwd(bw["dfeats"], ws["x_fin"], ws["cls_ln"], ws["st_post"], ws["st_pp"], P_["backbone.post_layernorm.weight"],
                      P_["backbone.post_layernorm.bias"], P_["post_post_layernorm.weight"], bw["dx"], bw["dcls"],
-                     G("backbone.post_layernorm.weight"), G("backbone.post_layernorm.bias"), G("post_post_layernorm.weight"),
-                     G("post_post_layernorm.bias"), B, P, Tp, D, partials=bw["part"], dx_bf16=bw["dxb"],
-                     dx_colsum=G(tl + "mlp.fc2.bias") if cfg.trainable_layer() == cfg.layers - 1 else None)     # (dx here = d(output of the last layer))
+                     G("backbone.post_layernorm.weight") if t_pl else sink[:D], G("backbone.post_layernorm.bias") if t_pl else sink[D:2 * D],
+                     G("post_post_layernorm.weight") if t_ppl else sink[2 * D:3 * D], G("post_post_layernorm.bias") if t_ppl else sink[3 * D:4 * D],
+                     B, P, Tp, D, partials=bw["part"], dx_bf16=bw["dxb"],
+                     dx_colsum=G(LP(last) + "mlp.fc2.bias") if last in tls else None)     # (dx here = d(output of the last layer))
+    if low is None:
+        return
     scale = cfg.head_dim ** -0.5
     # (bw["dxb"] always holds the bf16 copy of bw["dx"]: every kernel that writes dx writes it too -- no separate cast pass)
-    # ---- frozen layers ABOVE the trainable one (literal "layers.11" rule on a deeper model): dX only ----------
-    # Like the encoder forward (models.OwlViT._forward_impl), this chain couples no two images: it runs as sub-batches (row ranges of the
-    # same buffers) on the model's streams, layer by layer.
-    upper = range(cfg.layers - 1, cfg.trainable_layer(), -1)
-    if len(upper) > 0:
+
+    def dx_only(layers):
+        """A run of frozen layers the chain crosses (e.g. those above layer 11 under the literal "layers.11" rule on a deeper model): dX only.
+        Like the encoder forward (models.OwlViT._forward_impl), this chain couples no two images: it runs as sub-batches (row ranges of the
+        same buffers) on the model's streams, layer by layer."""
         chunks = model._encoder_chunks(B)
         main = torch.cuda.current_stream()
         streams = [main] + [S(c) for c in range(1, len(chunks))]
@@ -280,9 +348,9 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
             fork.record(main)
             for s_ in streams[1:]:
                 s_.wait_event(fork)
-        for i in upper:
+        for i in layers:
             Ls, fz = model._layer_ws(B, i), model._fz
-            pre = f"backbone.encoder.layers.{i}."
+            pre = LP(i)
             for (b0, nb), s_ in zip(chunks, streams):
                 r0, Mc = b0 * Tp, nb * Tp
                 R = lambda t: t[r0:r0 + Mc]
@@ -302,58 +370,98 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
             if c > 0:
                 J(c).record(s_)
                 main.wait_event(J(c))
-    Lt = model._layer_ws(B, cfg.trainable_layer())
-    # ---- trainable encoder layer ------------------------------------------------------------------------------
-    # Two chains: dX (this stream) and the four weight gradients.  A weight gradient feeds nothing downstream -- it only has to be in the
-    # bucket when backward() returns -- so the dW GEMMs (+ their bias column sums and slab reductions) run on the model's side stream, each
-    # behind the event of the dX-chain kernel that produces its operand: its workgroups fill the CUs the dX kernels' last rounds leave
-    # idle, and vice versa.  Same kernels on the same operands: same bits.  The side stream owns the split-K slab from here on and has its
-    # own reduction scratch; the second bf16 dx goes to its own buffer because dW(fc2) may still be reading the first.
-    main = torch.cuda.current_stream()
-    side = S(1) if model.encoder_streams > 1 else main
-    evs = model._dw_events
 
-    def on_side(k, fn):
-        if side is main:
-            fn()
+    def train(i, fc2_bias_done, goes_on, train_below):
+        """Trainable encoder layer i.  fc2_bias_done: the kernel that produced dx already summed its columns into this layer's fc2 bias gradient;
+        goes_on: the chain continues below this layer (its LayerNorm 1 backward then also emits dx); train_below: ... into a trainable layer, whose fc2
+        bias gradient that kernel sums on the way."""
+        # Two chains: dX (this stream) and the four weight gradients.  A weight gradient feeds nothing downstream -- it only has to be in the
+        # bucket when backward() returns -- so the dW GEMMs (+ their bias column sums and slab reductions) run on the model's side stream, each
+        # behind the event of the dX-chain kernel that produces its operand: its workgroups fill the CUs the dX kernels' last rounds leave
+        # idle, and vice versa.  Same kernels on the same operands: same bits.  The side stream owns the split-K slab from here on and has its
+        # own reduction scratch; the second bf16 dx goes to its own buffer because dW(fc2) may still be reading the first.  The side stream is
+        # in-order: the dW chains of successive trainable layers queue behind each other on the one set of scratch.
+        tl, Lt = LP(i), model._layer_ws(B, i)
+        main = torch.cuda.current_stream()
+        side = S(1) if model.encoder_streams > 1 else main
+        evs = model._dw_events
+
+        def on_side(k, fn):
+            if side is main:
+                fn()
+                return
+            evs[k].record(main)
+            side.wait_event(evs[k])
+            with torch.cuda.stream(side):
+                fn()
+
+        # MLP
+        if not fc2_bias_done:     # (the last layer's fc2 bias gradient came out of merge_ln_bwd, that of a layer below a trainable one out of its LayerNorm 1 backward)
+            ops.colsum_f32(bw["dx"], G(tl + "mlp.fc2.bias"), M, D, partials=bw["part"])
+        on_side(0, lambda: dW(bw["dxb"], Lt["g"], G(tl + "mlp.fc2.weight"), D, I, M, Mp, part="part2"))
+        dxc = 1 if side is main else 2          # (the weight-gradient GEMMs run beside the dX chain: ops.gemm's small-problem rule counts them)
+        ops.gemm(ops.EPI_DQGELU_BF16, bw["dxb"], wT(tl + "mlp.fc2.weight", D, I), bw["du"], aux=Lt["gp"], M=M, N=I, K=D, concurrency=dxc)
+        on_side(1, lambda: dW(bw["du"], Lt["h2"], G(tl + "mlp.fc1.weight"), I, D, M, Mp, G(tl + "mlp.fc1.bias"), part="part2"))
+        ops.gemm(ops.EPI_BIAS_BF16, bw["du"], wT(tl + "mlp.fc1.weight", I, D), bw["dh"], M=M, N=D, K=I, concurrency=dxc)
+        ops.layernorm_bwd(bw["dh"], Lt["x_mid"], Lt["st2"], P_[tl + "layer_norm2.weight"], bw["dx"], bw["dxm"],
+                          G(tl + "layer_norm2.weight"), G(tl + "layer_norm2.bias"), M, D, dx_bf16=bw["dxb2"], partials=bw["part"],
+                          dx_colsum=G(tl + "self_attn.out_proj.bias"))     # (dx here = d(x + out-proj output): its column sums are that bias's gradient)
+        # attention
+        on_side(2, lambda: dW(bw["dxb2"], Lt["att"], G(tl + "self_attn.out_proj.weight"), D, D, M, Mp, part="part2"))
+        woT = wT(tl + "self_attn.out_proj.weight", D, D)
+        ops.gemm(ops.EPI_BIAS_BF16, bw["dxb2"], woT, bw["datt"], M=M, N=D, K=D, concurrency=dxc)
+        ops.attention_bwd(Lt["qkv"], bw["datt"], Lt["att"], Lt["lse"], bw["dvec"], bw["dqkv"], B, H, T, Tp,
+                          cfg.head_dim ** -0.5)
+        o = model.flat_offsets[tl + "self_attn.q_proj.weight"]
+        g_wqkv = model.flat_grad[o: o + 3 * D * D].view(3 * D, D)
+        ob = model.flat_offsets[tl + "self_attn.q_proj.bias"]
+        g_bqkv = model.flat_grad[ob: ob + 3 * D]
+        on_side(3, lambda: dW(bw["dqkv"], Lt["h1"], g_wqkv, 3 * D, D, M, Mp, g_bqkv, part="part2"))
+        wqkv = model.flat_bf16[o: o + 3 * D * D].view(3 * D, D)
+        if pre_wt is not None:
+            wqkvT = pre_wt[tl + "qkv"]
+        else:
+            wqkvT = bw["wT"][: 3 * D * D].view(D, 3 * D)
+            ops.transpose_bf16(wqkv, wqkvT, 3 * D, D)
+        ops.gemm(ops.EPI_BIAS_BF16, bw["dqkv"], wqkvT, bw["dh"], M=M, N=D, K=3 * D, concurrency=dxc)
+        if not goes_on:
+            # everything below layer_norm1 is frozen: only its affine parameters need gradients
+            ops.layernorm_bwd(bw["dh"], Lt["x_in"], Lt["st1"], P_[tl + "layer_norm1.weight"], None, None,
+                              G(tl + "layer_norm1.weight"), G(tl + "layer_norm1.bias"), M, D, partials=bw["part"])
+            if side is not main:
+                evs[4].record(side)
+                main.wait_event(evs[4])
             return
-        evs[k].record(main)
-        side.wait_event(evs[k])
-        with torch.cuda.stream(side):
-            fn()
+        # The chain goes on: LayerNorm 1's backward writes the dx / bf16 dx the weight-gradient chain of this layer is still reading (dW(fc2)), and the
+        # layer below rewrites du / dxb2 / dqkv -- so the join with the side stream comes first (dW(qkv) has run beside the GEMM above).
+        if side is not main:
+            evs[4].record(side)
+            main.wait_event(evs[4])
+        ops.layernorm_bwd(bw["dh"], Lt["x_in"], Lt["st1"], P_[tl + "layer_norm1.weight"], bw["dxm"], bw["dx"],
+                          G(tl + "layer_norm1.weight"), G(tl + "layer_norm1.bias"), M, D, dx_bf16=bw["dxb"], partials=bw["part"],
+                          dx_colsum=G(LP(i - 1) + "mlp.fc2.bias") if train_below else None)     # (dx here = d(output of layer i - 1))
 
-    # MLP
-    if cfg.trainable_layer() != cfg.layers - 1:     # (the last layer's fc2 bias gradient came out of merge_ln_bwd)
-        ops.colsum_f32(bw["dx"], G(tl + "mlp.fc2.bias"), M, D, partials=bw["part"])
-    on_side(0, lambda: dW(bw["dxb"], Lt["g"], G(tl + "mlp.fc2.weight"), D, I, M, Mp, part="part2"))
-    dxc = 1 if side is main else 2          # (the weight-gradient GEMMs run beside the dX chain: ops.gemm's small-problem rule counts them)
-    ops.gemm(ops.EPI_DQGELU_BF16, bw["dxb"], wT(tl + "mlp.fc2.weight", D, I), bw["du"], aux=Lt["gp"], M=M, N=I, K=D, concurrency=dxc)
-    on_side(1, lambda: dW(bw["du"], Lt["h2"], G(tl + "mlp.fc1.weight"), I, D, M, Mp, G(tl + "mlp.fc1.bias"), part="part2"))
-    ops.gemm(ops.EPI_BIAS_BF16, bw["du"], wT(tl + "mlp.fc1.weight", I, D), bw["dh"], M=M, N=D, K=I, concurrency=dxc)
-    ops.layernorm_bwd(bw["dh"], Lt["x_mid"], Lt["st2"], P_[tl + "layer_norm2.weight"], bw["dx"], bw["dxm"],
-                      G(tl + "layer_norm2.weight"), G(tl + "layer_norm2.bias"), M, D, dx_bf16=bw["dxb2"], partials=bw["part"],
-                      dx_colsum=G(tl + "self_attn.out_proj.bias"))     # (dx here = d(x + out-proj output): its column sums are that bias's gradient)
-    # attention
-    on_side(2, lambda: dW(bw["dxb2"], Lt["att"], G(tl + "self_attn.out_proj.weight"), D, D, M, Mp, part="part2"))
-    woT = wT(tl + "self_attn.out_proj.weight", D, D)
-    ops.gemm(ops.EPI_BIAS_BF16, bw["dxb2"], woT, bw["datt"], M=M, N=D, K=D, concurrency=dxc)
-    ops.attention_bwd(Lt["qkv"], bw["datt"], Lt["att"], Lt["lse"], bw["dvec"], bw["dqkv"], B, H, T, Tp,
-                      cfg.head_dim ** -0.5)
-    o = model.flat_offsets[tl + "self_attn.q_proj.weight"]
-    g_wqkv = model.flat_grad[o: o + 3 * D * D].view(3 * D, D)
-    ob = model.flat_offsets[tl + "self_attn.q_proj.bias"]
-    g_bqkv = model.flat_grad[ob: ob + 3 * D]
-    on_side(3, lambda: dW(bw["dqkv"], Lt["h1"], g_wqkv, 3 * D, D, M, Mp, g_bqkv, part="part2"))
-    wqkv = model.flat_bf16[o: o + 3 * D * D].view(3 * D, D)
-    if pre_wt is not None:
-        wqkvT = pre_wt["qkv"]
-    else:
-        wqkvT = bw["wT"][: 3 * D * D].view(D, 3 * D)
-        ops.transpose_bf16(wqkv, wqkvT, 3 * D, D)
-    ops.gemm(ops.EPI_BIAS_BF16, bw["dqkv"], wqkvT, bw["dh"], M=M, N=D, K=3 * D, concurrency=dxc)
-    # everything below layer_norm1 is frozen: only its affine parameters need gradients
-    ops.layernorm_bwd(bw["dh"], Lt["x_in"], Lt["st1"], P_[tl + "layer_norm1.weight"], None, None,
-                      G(tl + "layer_norm1.weight"), G(tl + "layer_norm1.bias"), M, D, partials=bw["part"])
-    if side is not main:
-        evs[4].record(side)
-        main.wait_event(evs[4])
+    # ---- the encoder, from the last layer down to the floor: each layer either trained or crossed ----------------------------------------
+    i = last
+    while i >= low:
+        if i in tls:
+            train(i, fc2_bias_done=(i == last or (i + 1) in tls), goes_on=(i > low or below_enc), train_below=(i - 1 >= low and (i - 1) in tls))
+            i -= 1
+        else:
+            run = []
+            while i >= low and i not in tls:
+                run.append(i)
+                i -= 1
+            dx_only(run)
+    if not below_enc:
+        return
+    # ---- below layer 0: pre_layernorm and the embeddings (bw["dx"] = d(output of pre_layernorm), f32) ----------------------------------------
+    pw = model._pre_ws(B)
+    t_pre, t_emb = model._train_pre, model._train_emb
+    ops.layernorm_bwd(bw["dx"], pw["x_emb"], pw["st_pre"], P_["backbone.pre_layernorm.weight"], None, bw["dxm"] if t_emb else None,
+                      G("backbone.pre_layernorm.weight") if t_pre else None, G("backbone.pre_layernorm.bias") if t_pre else None, M, D, partials=bw["part"])
+    if t_emb:
+        ops.embed_bwd(bw["dxm"], G("backbone.embeddings.position_embedding.weight"), G("backbone.embeddings.class_embedding"), pw["dE"], B, T, Tp, D)
+        ops.im2row_bf16(ws["img"], pw["patches"], B, cfg.image_size, cfg.patch_size)
+        patch_weight_grad(pw["dE"], pw["patches"], G("backbone.embeddings.patch_embedding.weight").view(D, cfg.patch_k), D, cfg.patch_k, Mh,
+                          scratch=dict(slab=bw["slab"], tA=bw["tAh"], tB=bw["tBh"]))

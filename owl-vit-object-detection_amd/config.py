@@ -72,17 +72,31 @@ class OwlConfig:
         """Index selected by the literal substring rule ``"layers.11" in name``."""
         return 11
 
-    def flops_backward(self) -> float:
+    def flops_backward(self, trainable_layers=None, floor=None) -> float:
+        """Default: the reference set.  Another set is stated by its trainable encoder layers and the floor of its dX chain (models.OwlViT's
+        `trainable_layers` / `backward_floor`); the heads count 2x whichever of them train."""
         # trainable layer: dX + dW = 2x its forward; frozen layers above it: dX only
         # (linear 1x, attention 2x of their forward parts); heads 2x.
         T, D, I = self.tokens, self.hidden, self.mlp
         lin = 8.0 * T * D * D + 4.0 * T * D * I
         att = 4.0 * T * T * D
-        above = self.layers - 1 - self.trainable_layer()
-        return 2.0 * self.flops_layer() + above * (lin + 2.0 * att) + 2.0 * self.flops_heads()
+        if trainable_layers is None and floor is None:
+            above = self.layers - 1 - self.trainable_layer()
+            return 2.0 * self.flops_layer() + above * (lin + 2.0 * att) + 2.0 * self.flops_heads()
+        tls = tuple(sorted(trainable_layers or ()))
+        floor = (tls[0] if tls else "heads") if floor is None else floor
+        if floor in ("heads", "post_post_layernorm", "post_layernorm"):
+            return 2.0 * self.flops_heads()
+        low = floor if isinstance(floor, int) else 0          # lowest layer the chain crosses
+        crossed = self.layers - low - len([i for i in tls if i >= low])
+        # (a trainable layer counts 2x its forward wherever it sits, as in the default: its LayerNorm 1 needs the dX through QKV either way)
+        total = 2.0 * self.flops_heads() + crossed * (lin + 2.0 * att) + len([i for i in tls if i >= low]) * 2.0 * self.flops_layer()
+        if floor == "embeddings":
+            total += 2.0 * self.patches * self.patch_k * self.hidden          # the patch-embedding weight gradient
+        return total
 
-    def flops_train_step(self) -> float:
-        return self.flops_forward() + self.flops_backward()
+    def flops_train_step(self, trainable_layers=None, floor=None) -> float:
+        return self.flops_forward() + self.flops_backward(trainable_layers, floor)
 
 
 CONFIGS = {

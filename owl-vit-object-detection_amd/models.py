@@ -46,25 +46,43 @@ class _Node(nn.Module):
     """Bare container so that parameter names match the reference module tree."""
 
 
-def _flat_order(cfg: OwlConfig):
-    """Order of the trainable tensors inside the flat bucket (q,k,v adjacent -> fused views)."""
-    tl = f"backbone.encoder.layers.{cfg.trainable_layer()}."
-    names = ["queries"]
-    names += [tl + f"self_attn.{p}_proj.weight" for p in "qkv"] + [tl + f"self_attn.{p}_proj.bias" for p in "qkv"]
-    names += [tl + "self_attn.out_proj.weight", tl + "self_attn.out_proj.bias", tl + "layer_norm1.weight", tl + "layer_norm1.bias",
-              tl + "mlp.fc1.weight", tl + "mlp.fc1.bias", tl + "mlp.fc2.weight", tl + "mlp.fc2.bias",
-              tl + "layer_norm2.weight", tl + "layer_norm2.bias"]
-    names += ["backbone.post_layernorm.weight", "backbone.post_layernorm.bias", "post_post_layernorm.weight",
-              "post_post_layernorm.bias", "class_predictor.dense0.weight", "class_predictor.dense0.bias",
-              "box_head.dense0.weight", "box_head.dense0.bias", "box_head.dense1.weight", "box_head.dense1.bias",
-              "box_head.dense2.weight", "box_head.dense2.bias"]
+_LAYER_ORDER = ([f"self_attn.{p}_proj.weight" for p in "qkv"] + [f"self_attn.{p}_proj.bias" for p in "qkv"]
+                + ["self_attn.out_proj.weight", "self_attn.out_proj.bias", "layer_norm1.weight", "layer_norm1.bias", "mlp.fc1.weight", "mlp.fc1.bias",
+                   "mlp.fc2.weight", "mlp.fc2.bias", "layer_norm2.weight", "layer_norm2.bias"])
+_UNIT_ORDER = {
+    "queries": ["queries"],
+    "backbone.post_layernorm": ["backbone.post_layernorm.weight", "backbone.post_layernorm.bias"],
+    "post_post_layernorm": ["post_post_layernorm.weight", "post_post_layernorm.bias"],
+    "class_predictor.dense0": ["class_predictor.dense0.weight", "class_predictor.dense0.bias"],
+    "box_head": ["box_head.dense0.weight", "box_head.dense0.bias", "box_head.dense1.weight", "box_head.dense1.bias", "box_head.dense2.weight", "box_head.dense2.bias"],
+    "backbone.pre_layernorm": ["backbone.pre_layernorm.weight", "backbone.pre_layernorm.bias"],
+    "backbone.embeddings": ["backbone.embeddings.class_embedding", "backbone.embeddings.patch_embedding.weight", "backbone.embeddings.position_embedding.weight"],
+}
+
+
+def _flat_order(cfg: OwlConfig, trainable=None):
+    """Order of the trainable tensors inside the flat bucket (q,k,v adjacent -> fused views).  `trainable`: the substring list of the freeze rule (None = the
+    reference's).  Units follow weights.BUCKET_UNITS -- queries, the trainable encoder layers in ascending order, post_layernorm, post_post_layernorm, the class
+    head, the box head, pre_layernorm, the embeddings -- so the reference set keeps the layout its checkpoints and optimizer states were written with."""
+    units, layers = W.trainable_units(cfg, trainable)
+    names = []
+    for u in W.BUCKET_UNITS:
+        if u == "layers":
+            for i in layers:
+                names += [f"backbone.encoder.layers.{i}." + n for n in _LAYER_ORDER]
+        elif u in units:
+            names += _UNIT_ORDER[u]
     return names
 
 
 class OwlViT(nn.Module):
     """Vision-only OWL-ViT with a learnable query bank (ref src/models.py:41-119)."""
 
-    def __init__(self, cfg: OwlConfig, state: "dict[str, np.ndarray]", device="cuda", encoder_streams: int = 2):
+    def __init__(self, cfg: OwlConfig, state: "dict[str, np.ndarray]", device="cuda", encoder_streams: int = 2, trainable=None):
+        """trainable: None = the reference's freeze rule (weights.FREEZE_KEEP); otherwise an iterable of substrings with the reference's semantics -- a
+        parameter is trainable iff any of them occurs in its name ("layers.1" therefore selects layers 1 AND 10 to 19).  The selection must be made of whole
+        units (weights.BUCKET_UNITS: queries, class_predictor.dense0, box_head, backbone.post_layernorm, post_post_layernorm, each encoder layer,
+        backbone.pre_layernorm, backbone.embeddings); a partial unit or an empty selection raises ValueError."""
         super().__init__()
         self.cfg = cfg
         self.device_ = torch.device(device)
@@ -82,8 +100,16 @@ class OwlViT(nn.Module):
         missing = set(shapes) - set(state)
         if missing:
             raise KeyError(f"missing parameters: {sorted(missing)[:4]} ...")
-        order = _flat_order(cfg)
-        assert set(order) == {n for n in shapes if W.is_trainable(n)}, "flat order must cover the trainable set"
+        self._keep = None if trainable is None else tuple(trainable)
+        keep = W.FREEZE_KEEP if self._keep is None else self._keep
+        units, self.trainable_layers = W.trainable_units(cfg, self._keep)
+        self._units, self._tl_set = frozenset(units), frozenset(self.trainable_layers)
+        self.backward_floor = W.backward_floor(units)          # the lowest point the backward's dX chain reaches
+        # lowest encoder layer the dX chain crosses (None: the chain ends above the encoder)
+        self._chain_low = self.backward_floor if isinstance(self.backward_floor, int) else (0 if self.backward_floor in ("pre_layernorm", "embeddings") else None)
+        self._train_emb, self._train_pre = "backbone.embeddings" in units, "backbone.pre_layernorm" in units
+        order = _flat_order(cfg, self._keep)
+        assert set(order) == {n for n in shapes if W.is_trainable(n, keep)}, "flat order must cover the trainable set"
 
         # ---- flat trainable bucket (f32) + grad bucket; every tensor starts 8-element aligned ----
         offs, off = OrderedDict(), 0
@@ -119,9 +145,22 @@ class OwlViT(nn.Module):
         with torch.no_grad():
             # im2row-free for every patch size (L/14's 14-pixel rows included): the weight goes into the gather loader's K order once (weights.py)
             wpe = W.patch_weight_gather_layout(P_["backbone.embeddings.patch_embedding.weight"].detach(), cfg.patch_size)
-            self._fz["w_pe"] = wpe.to(torch.bfloat16).contiguous()
+            self._pe_gather = None
+            if not self._train_emb:
+                self._fz["w_pe"] = wpe.to(torch.bfloat16).contiguous()
+            elif wpe.shape[1] == cfg.patch_k:
+                # trainable, 2^n patch size: the gather order is the parameter's own -> the forward reads the bucket's bf16 copy where it lies
+                self._fz["w_pe"] = self._tview("backbone.embeddings.patch_embedding.weight").view(D, cfg.patch_k)
+            else:
+                # trainable, other patch sizes: a per-step product of the bucket (_refresh_patch_weight), re-laid out by one column gather / scatter; the
+                # column map comes from the same function that lays the frozen weight out
+                cols = W.patch_weight_gather_layout(np.arange(1, cfg.patch_k + 1, dtype=np.float32)[None, :], cfg.patch_size)[0]
+                dst = np.nonzero(cols)[0]
+                self._pe_gather = (torch.as_tensor(dst, dtype=torch.int64, device=self.device_),
+                                   torch.as_tensor(cols[dst].astype(np.int64) - 1, device=self.device_))
+                self._fz["w_pe"] = torch.zeros(D, wpe.shape[1], dtype=torch.bfloat16, device=self.device_)
             for i in range(cfg.layers):
-                if i == cfg.trainable_layer():
+                if i in self._tl_set:
                     continue
                 pre = f"backbone.encoder.layers.{i}."
                 self._fz[f"{i}.wqkv"] = torch.cat([P_[pre + f"self_attn.{p}_proj.weight"] for p in "qkv"], 0).to(torch.bfloat16).contiguous()
@@ -129,11 +168,17 @@ class OwlViT(nn.Module):
                 self._fz[f"{i}.wo"] = P_[pre + "self_attn.out_proj.weight"].to(torch.bfloat16).contiguous()
                 self._fz[f"{i}.w1"] = P_[pre + "mlp.fc1.weight"].to(torch.bfloat16).contiguous()
                 self._fz[f"{i}.w2"] = P_[pre + "mlp.fc2.weight"].to(torch.bfloat16).contiguous()
-                if i > cfg.trainable_layer():
-                    # frozen layers ABOVE the trainable one (the literal "layers.11" rule on a deeper model, ref
-                    # src/models.py:175): the backward passes through them (dX only) -> static transposed copies
+                if self._chain_low is not None and i >= self._chain_low:
+                    # frozen layers the backward's dX chain crosses (e.g. those above layer 11 under the literal "layers.11" rule on a deeper
+                    # model, ref src/models.py:175): the backward passes through them (dX only) -> static transposed copies
                     for k in ("wqkv", "wo", "w1", "w2"):
                         self._fz[f"{i}.{k}T"] = self._fz[f"{i}.{k}"].t().contiguous()
+            # frozen heads: bf16 compute copies of their GEMM weights and, where the dX chain crosses them, the transposed copies -- made once, here
+            for n in ("class_predictor.dense0.weight", "box_head.dense0.weight", "box_head.dense1.weight"):
+                if n not in offs:
+                    self._fz[n] = P_[n].to(torch.bfloat16).contiguous()
+                    if self.backward_floor != "heads":
+                        self._fz[n + ".T"] = self._fz[n].t().contiguous()
         self.box_bias = box_bias_table(cfg.grid).to(self.device_)
         self._ws = {}
         self._gen = 0                      # generation of the latest forward (any batch size): see _forward_impl / autograd.OwlViTFunction
@@ -192,11 +237,15 @@ class OwlViT(nn.Module):
         src = self.flat_bf16 if dtype == torch.bfloat16 else self.flat_param
         return src[o: o + n].view(self._byname[name].shape)
 
+    def _hw(self, name: str):
+        """bf16 compute copy of a head GEMM weight: the bucket's view, or the frozen copy."""
+        return self._tview(name) if name in self.flat_offsets else self._fz[name]
+
     def _layer_weights(self, i: int):
         cfg, D = self.cfg, self.cfg.hidden
         pre = f"backbone.encoder.layers.{i}."
         P_ = self._byname
-        if i == cfg.trainable_layer():
+        if i in self._tl_set:
             o = self.flat_offsets[pre + "self_attn.q_proj.weight"]
             wqkv = self.flat_bf16[o: o + 3 * D * D].view(3 * D, D)
             ob = self.flat_offsets[pre + "self_attn.q_proj.bias"]
@@ -281,7 +330,7 @@ class OwlViT(nn.Module):
         return ws
 
     def _layer_ws(self, B: int, i: int):
-        """Saved activations of layer i (i >= trainable layer) for the backward; allocated once per batch size."""
+        """Saved activations of layer i (a layer the backward's dX chain crosses) for the backward; allocated once per batch size."""
         key = ("layer", B, i)
         if key in self._ws:
             return self._ws[key]
@@ -294,22 +343,46 @@ class OwlViT(nn.Module):
                  qkv=z(M, 3 * D, bf, dev), att=z(M, D, bf, dev),
                  lse=torch.zeros(B, cfg.heads, Tp, device=dev),
                  gp=z(M, I, bf, dev))          # quick_gelu'(u), saved by fc1's epilogue: what the dX GEMM through the activation multiplies by
-        if i == cfg.trainable_layer():   # dW operands
+        if i in self._tl_set:   # dW operands
             L.update(h1=z(M, D, bf, dev), h2=z(M, D, bf, dev), g=z(M, I, bf, dev))
         self._ws[key] = L
         return L
 
+    def _pre_ws(self, B: int):
+        """Kept by a gradient-recording forward when pre_layernorm or the embeddings train: the input of pre_layernorm and its row statistics; with trainable
+        embeddings also the patch rows of the image (the patch-embedding weight gradient's X operand) and the packed bf16 gradient rows."""
+        key = ("pre", B)
+        if key in self._ws:
+            return self._ws[key]
+        cfg, dev = self.cfg, self.device_
+        M, Mh = B * cfg.tokens_padded, B * cfg.patches
+        L = dict(x_emb=ops.zeros_rows(M, cfg.hidden, torch.float32, dev), st_pre=torch.zeros(M, 2, device=dev))
+        if self._train_emb:
+            L.update(patches=ops.zeros_rows(Mh, (cfg.patch_k + 7) // 8 * 8, torch.bfloat16, dev), dE=ops.zeros_rows(Mh, cfg.hidden, torch.bfloat16, dev))
+        self._ws[key] = L
+        return L
+
     def _wt_specs(self):
-        """(name, rows, cols) of every trainable weight the backward needs transposed (autograd.backward_impl)."""
+        """(key, rows, cols) of every trainable weight the backward needs transposed (autograd.backward_impl): a parameter name, or `<layer prefix>qkv` for
+        a layer's fused q / k / v weight."""
         cfg = self.cfg
         D, I, Dt = cfg.hidden, cfg.mlp, cfg.text_dim
-        tl = f"backbone.encoder.layers.{cfg.trainable_layer()}."
-        return [("class_predictor.dense0.weight", Dt, D), ("box_head.dense1.weight", D, D), ("box_head.dense0.weight", D, D), (tl + "mlp.fc2.weight", D, I),
-                (tl + "mlp.fc1.weight", I, D), (tl + "self_attn.out_proj.weight", D, D), ("qkv", 3 * D, D)]
+        specs = [(n, r, c) for n, r, c in (("class_predictor.dense0.weight", Dt, D), ("box_head.dense1.weight", D, D), ("box_head.dense0.weight", D, D))
+                 if n in self.flat_offsets and self.backward_floor != "heads"]
+        for i in sorted(self.trainable_layers, reverse=True):
+            tl = f"backbone.encoder.layers.{i}."
+            specs += [(tl + "mlp.fc2.weight", D, I), (tl + "mlp.fc1.weight", I, D), (tl + "self_attn.out_proj.weight", D, D), (tl + "qkv", 3 * D, D)]
+        return specs
+
+    def _wqkv(self, i: int):
+        """bf16 [3D, D] view of trainable layer i's fused q / k / v weight."""
+        D = self.cfg.hidden
+        o = self.flat_offsets[f"backbone.encoder.layers.{i}.self_attn.q_proj.weight"]
+        return self.flat_bf16[o: o + 3 * D * D].view(3 * D, D)
 
     def _pretranspose_weights(self):
         """Launch the backward's weight transposes now, on their own stream (called by a gradient-recording forward on the stream that has just ordered itself
-        behind any deferred optimizer step, right before the trainable layer).  The backward waits for `_wt_event` and reads `_wt[name]`."""
+        behind any deferred optimizer step, right before the first trainable layer).  The backward waits for `_wt_event` and reads `_wt[key]`."""
         if self._wt is None:
             self._wt = {n: torch.empty(c, r, dtype=torch.bfloat16, device=self.device_) for n, r, c in self._wt_specs()}
             self._wt_stream_ = torch.cuda.Stream(device=self.device_)
@@ -317,17 +390,20 @@ class OwlViT(nn.Module):
         s_ = self._wt_stream_
         s_.wait_stream(cur)                       # (the bf16 compute copies are current on `cur`; a previous backward's reads of these buffers precede this point on it too)
         with torch.cuda.stream(s_):
-            D = self.cfg.hidden
             for n, r, c in self._wt_specs():
-                if n == "qkv":
-                    o = self.flat_offsets[f"backbone.encoder.layers.{self.cfg.trainable_layer()}.self_attn.q_proj.weight"]
-                    src = self.flat_bf16[o: o + 3 * D * D].view(3 * D, D)
-                else:
-                    src = self._tview(n)
+                src = self._wqkv(int(n.split(".")[3])) if n.endswith(".qkv") else self._tview(n)
                 ops.transpose_bf16(src, self._wt[n], r, c)
             ev = torch.cuda.Event()
             ev.record(s_)
         self._wt_event = ev
+
+    def _refresh_patch_weight(self):
+        """Trainable patch embedding with a patch size that is not 2^n: the forward's gather-layout weight follows the bucket's bf16 copy (every forward calls
+        this right after that copy is known to be current, so it obeys the same staleness rule)."""
+        if self._pe_gather is not None:
+            dst, src = self._pe_gather
+            w = self._tview("backbone.embeddings.patch_embedding.weight").view(self.cfg.hidden, self.cfg.patch_k)
+            self._fz["w_pe"].index_copy_(1, dst, w.index_select(1, src))
 
     def refresh_compute_weights(self, force: bool = True):
         """bf16 copies of the trainable tensors: one cast over the flat bucket.  Every forward calls it, except the first forward after a
@@ -336,6 +412,7 @@ class OwlViT(nn.Module):
         this method after such a write."""
         ops.cast_bf16(self.flat_param, self.flat_bf16)
         self._bf16_current = False
+        self._refresh_patch_weight()
 
     def _mark_bf16_current(self):
         """optim.FusedAdamW.step only: its kernel has just rewritten flat_bf16 from the updated flat_param."""
@@ -367,21 +444,25 @@ class OwlViT(nn.Module):
 
     def _wait_params(self):
         """Order the compute stream behind a deferred optimizer step (ddp.DataParallel(overlap=True)): called right before the
-        first trainable tensor is read, i.e. after the frozen prefix (embeddings + encoder layers below the trainable one)."""
+        first trainable tensor is read, i.e. after the frozen prefix (under the reference rule: embeddings + encoder layers below the trainable one;
+        with trainable embeddings or pre_layernorm there is no such prefix)."""
         if self._param_event is not None:
             torch.cuda.current_stream().wait_event(self._param_event)
             self._param_event = None
 
     def _check_trainable_set(self):
-        """The backward is built for exactly the reference's freeze rule (ref src/models.py:173-184).  The reference's rule is a
-        user-editable loop over requires_grad; here a different set would silently get no gradient (or still be updated by the
-        optimizer), so a mismatch is an error rather than a silent difference."""
+        """The backward is built at construction for one trainable set (`trainable=`; default: the reference's freeze rule, ref
+        src/models.py:173-184).  The reference's rule is a user-editable loop over requires_grad; here a different set would silently
+        get no gradient (or still be updated by the optimizer), so a mismatch is an error rather than a silent difference."""
         for n, p in self._byname.items():
             if p.requires_grad != (n in self._trainable):
                 raise RuntimeError(
                     f"parameter `{n}` has requires_grad={p.requires_grad}, but this build's hand-written backward computes gradients for "
-                    "exactly the reference's trainable set (layers.11 / box / post_layernorm / class_predictor / queries, ref "
-                    "src/models.py:173-184); freezing or unfreezing individual tensors is not supported")
+                    + ("exactly the reference's trainable set (layers.11 / box / post_layernorm / class_predictor / queries, ref "
+                       "src/models.py:173-184)" if self._keep is None else
+                       f"exactly the trainable set this model was built with (trainable={self._keep!r})")
+                    + "; freezing or unfreezing individual tensors is not supported.  Choose the trainable set at construction: "
+                    "load_model(..., trainable=[...]) / OwlViT(..., trainable=[...]).")
 
     # -- encoder schedule --------------------------------------------------------------------------------
     def _encoder_chunks(self, B: int):
@@ -429,13 +510,12 @@ class OwlViT(nn.Module):
         b0, nb = st["b0"], st["nb"]
         r0, M = b0 * Tp, nb * Tp
         R = lambda t: t[r0:r0 + M]
-        tl = cfg.trainable_layer()
         scale = cfg.head_dim ** -0.5
         xs, pending, pending1 = st["xs"], st["pending"], st["pending1"]
         d1, d2 = R(ws["d1"]), R(ws["d2"])
         lw = self._layer_weights(i)
-        sv = save and i >= tl          # the backward passes through this layer: keep its activations
-        full = sv and i == tl          # ... and, for the trainable layer, the dW operands too
+        sv = save and self._chain_low is not None and i >= self._chain_low          # the backward passes through this layer: keep its activations
+        full = sv and i in self._tl_set          # ... and, for a trainable layer, the dW operands too
         Ls = self._layer_ws(B, i) if sv else None
         st1 = R(Ls["st1"]) if sv else None
         h = R(Ls["h1"]) if full else R(ws["h"])
@@ -490,9 +570,17 @@ class OwlViT(nn.Module):
         P_ = self._byname
         if self._bf16_current and self._bf16_version == self.flat_param._version:
             self._bf16_current = False          # one-shot: the fused AdamW's own bf16 pass covers exactly this forward
+            from_optimizer = True
         else:
+            from_optimizer = False
             self._wait_params()
             self.refresh_compute_weights()
+        if self._train_emb or self._train_pre:
+            # the first trainable tensor is read by the embeddings (and a deferred tail's backward may still be reading the kept bf16 image): nothing of this
+            # forward runs under a deferred tail
+            self._wait_params()
+            if from_optimizer:
+                self._refresh_patch_weight()        # (the other branch above has done it: refresh_compute_weights)
 
         if image.dtype == torch.float32:
             ops.cast_bf16(image.contiguous(), ws["img"])
@@ -503,21 +591,35 @@ class OwlViT(nn.Module):
             raise TypeError("image must be float32 or bfloat16")
 
         x = ws["x"]
-        ops.patch_embed(img, self._fz["w_pe"], P_["backbone.embeddings.position_embedding.weight"], x, B, cfg.image_size,
-                        cfg.patch_size, D, Tp, scratch=self._patch_scratch(B))
-        ops.cls_rows(x, P_["backbone.embeddings.class_embedding"], P_["backbone.embeddings.position_embedding.weight"], B, Tp, D)
-        ops.layernorm(x, P_["backbone.pre_layernorm.weight"], P_["backbone.pre_layernorm.bias"], x, M, D, eps=cfg.ln_eps)
+        low = save and self.backward_floor in ("pre_layernorm", "embeddings")
+        if low:
+            # the backward goes below layer 0: keep pre_layernorm's input and row statistics (and, for the patch-embedding weight gradient, the bf16 image)
+            pw = self._pre_ws(B)
+            if self._train_emb and img is not ws["img"]:
+                ws["img"].copy_(img)
+            x_emb = pw["x_emb"]
+            ops.patch_embed(img, self._fz["w_pe"], P_["backbone.embeddings.position_embedding.weight"], x_emb, B, cfg.image_size,
+                            cfg.patch_size, D, Tp, scratch=self._patch_scratch(B))
+            ops.cls_rows(x_emb, P_["backbone.embeddings.class_embedding"], P_["backbone.embeddings.position_embedding.weight"], B, Tp, D)
+            ops.layernorm(x_emb, P_["backbone.pre_layernorm.weight"], P_["backbone.pre_layernorm.bias"], x, M, D, pw["st_pre"], cfg.ln_eps)
+        else:
+            ops.patch_embed(img, self._fz["w_pe"], P_["backbone.embeddings.position_embedding.weight"], x, B, cfg.image_size,
+                            cfg.patch_size, D, Tp, scratch=self._patch_scratch(B))
+            ops.cls_rows(x, P_["backbone.embeddings.class_embedding"], P_["backbone.embeddings.position_embedding.weight"], B, Tp, D)
+            ops.layernorm(x, P_["backbone.pre_layernorm.weight"], P_["backbone.pre_layernorm.bias"], x, M, D, eps=cfg.ln_eps)
 
         # ---- encoder.  No kernel of it couples images, so the batch is run as `encoder_streams` sub-batches (contiguous row ranges of the
         #      same buffers), each on its own HIP stream, layer by layer: the idle CUs of one sub-batch's last GEMM round / attention tail
         #      run the other sub-batch's next kernel (a 256 x 256 GEMM workgroup owns its CU's registers and LDS, so the overlap is at CU
         #      granularity).  Measured on the forward: -3.7 % at B/16 batch 32, -2.9 % at L/14 batch 16 (two streams; three or four lose --
         #      profiles/r02_encoder_streams.md).  Every kernel is batch-invariant: same bits as the single-stream schedule.
-        tl = cfg.trainable_layer()
+        # first encoder layer that reads a trainable tensor (or keeps an activation the deferred tail's backward may still be reading): where the sub-batch
+        # streams wait for a deferred tail.  None: no encoder layer does; the wait then sits in front of the final LayerNorms.
+        tl = self._chain_low
         param_event, self._param_event = self._param_event, None
         chunks = self._encoder_chunks(B)
         main = torch.cuda.current_stream()
-        if save:        # first use allocates (and zero-fills, on THIS stream) the kept activations: before any other stream may write them
+        if save and tl is not None:        # first use allocates (and zero-fills, on THIS stream) the kept activations: before any other stream may write them
             for i in range(tl, cfg.layers):
                 self._layer_ws(B, i)
         if len(chunks) > 1:
@@ -543,15 +645,17 @@ class OwlViT(nn.Module):
                 self._join[c].record(st["stream"])
                 main.wait_event(self._join[c])
         # the sub-batches' residual streams / deferred MLP-branch outputs are row ranges of ONE buffer each: the merge kernel takes the batch
+        if tl is None and param_event is not None:
+            main.wait_event(param_event)            # heads-only sets: the whole encoder ran on frozen weights
         last = cfg.layers - 1
-        xs = self._layer_ws(B, last)["x_mid"] if (save and last >= tl) else x
+        xs = self._layer_ws(B, last)["x_mid"] if (save and tl is not None) else x
         assert all(st["xs"].data_ptr() == xs.data_ptr() + st["b0"] * Tp * D * 4 for st in states)
         pending = ws["d2"]
 
         # ---- final residual add + post_layernorm (all tokens) * class token -> post_post_layernorm
         #      (ref src/models.py:80-86); the final residual stream is materialised in `x` for the backward
         feats = ws["feats"]
-        tv = lambda n: self._tview(n)
+        tv = self._hw
         # (the backward reads the final residual stream; it gets a buffer of its own because with overlap_tail the NEXT forward's patch embedding
         #  rewrites `x` while this step's backward may still be running)
         ops.merge_ln(xs, P_["backbone.post_layernorm.weight"], P_["backbone.post_layernorm.bias"], P_["post_post_layernorm.weight"],
@@ -599,7 +703,7 @@ class OwlViT(nn.Module):
 
 
 def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed: int = 1234, state=None, *,
-               prompt_ids=None, text_state=None, vocab=None, merges=None):
+               prompt_ids=None, text_state=None, vocab=None, merges=None, trainable=None):
     """ref src/models.py:149-191.  The reference downloads `google/owlvit-base-patch32` and runs the
     CLIP text tower once to initialise the query bank; neither box has network access, so weights
     come from `state` (name -> array, reference parameter names) or, by default, the deterministic
@@ -615,7 +719,9 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
     `vocab` / `merges` (paths of the CLIP `vocab.json` / `merges.txt` every OWL-ViT checkpoint carries -- a download neither box can make, so they
     are not shipped): the three prompts per label are built and tokenised HERE exactly as the reference does (ref models.py:155-166 via
     tokenizer.ClipBPE, id for id `transformers.CLIPTokenizer`), i.e. the unchanged `load_model(labelmap, device)` call of ref main.py:42 plus the two
-    paths gives the reference's query bank."""
+    paths gives the reference's query bank.
+
+    `trainable` (None = the reference's freeze rule): the substring list of that rule, as a user of the reference would edit it -- see OwlViT."""
     n_classes = len(labelmap)
     cfg = get_config(arch, n_classes=n_classes)
     if (vocab is None) != (merges is None):
@@ -641,4 +747,4 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
         state = OrderedDict(state)
         state["queries"] = tower.query_bank(ids).cpu().numpy()
         del tower
-    return OwlViT(cfg, state, device)
+    return OwlViT(cfg, state, device, trainable=trainable)

@@ -275,6 +275,22 @@ def colsum_f32(src, colsum, R, C, partials=None):
     _lib.call("owl_colsum_f32", stream(), src, colsum, R, C, part, part.numel())
 
 
+def embed_bwd(dx, dpos, dcls, dE, B, T, Tp, D):
+    """Backward of the embeddings: dpos [T, D] += sum_b dx[b, t], dcls [D] += sum_b dx[b, 0], dE [B (T - 1), D] = bf16 patch rows of dx (no class / pad rows)."""
+    _chk(dx, torch.float32, "dx"); _chk(dpos, torch.float32, "dpos"); _chk(dcls, torch.float32, "dcls"); _chk(dE, torch.bfloat16, "dE")
+    if dx.numel() < B * Tp * D or dpos.numel() < T * D or dcls.numel() < D or dE.numel() < B * (T - 1) * D:
+        raise ValueError("embed_bwd: dx must hold [B, Tp, D], dpos [T, D], dcls [D], dE [B (T - 1), D]")
+    _lib.call("owl_embed_bwd", stream(), dx, dpos, dcls, dE, B, T, Tp, D)
+
+
+def im2row_bf16(image, out, B, S, ps):
+    """out [>= B (S / ps)^2, ld] bf16 <- patches of image [B, 3, S, S] bf16, columns in the conv weight's (c, i, j) order; columns past 3 ps^2 are left alone."""
+    _chk(image, torch.bfloat16, "image"); _chk(out, torch.bfloat16, "out")
+    if image.numel() < B * 3 * S * S or out.dim() != 2 or out.shape[0] < B * (S // ps) ** 2:
+        raise ValueError("im2row_bf16: image must hold [B, 3, S, S], out [>= B (S / ps)^2, ld]")
+    _lib.call("owl_im2row_bf16", stream(), image, out, out.shape[1], B, S, ps)
+
+
 def attention_bwd(qkv, dO, O, lse, dvec, dqkv, B, H, T, Tp, scale, phases=0):
     """phases: 0 = dvec + dK / dV + dQ on this stream; a mask (1 | 2 | 4) launches a subset (dK / dV and dQ only share inputs: tools/attn_bwd_overlap_ab.py)."""
     _lib.call("owl_attention_bwd_bf16", stream(), qkv, dO, O, lse, dvec, dqkv, B, H, T, Tp, float(scale), int(phases))

@@ -229,11 +229,18 @@ class FusedAdamW(torch.optim.Optimizer):
         keys = ("lr", "weight_decay", "initial_lr")          # (`initial_lr`: set by a torch LR scheduler at its construction)
         return dict(step=self.step_count, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr, betas=self.betas,
                     eps=self.eps, weight_decay=self.weight_decay, max_norm=self.max_norm,
+                    layout=list(self.model.flat_offsets.items()),          # (the bucket's tensors and offsets: the moments are meaningless under another trainable set)
                     groups=[{k: g[k] for k in keys if k in g} for g in self.param_groups])
 
     def load_state_dict(self, sd):
         """Moments and step count; the groups' lr / weight_decay / initial_lr and max_norm where the dict has them (one written before it had: not)."""
         self._sync_tail()
+        mine = list(self.model.flat_offsets.items())
+        theirs = [tuple(x) for x in sd["layout"]] if "layout" in sd else None
+        if (theirs is not None and theirs != mine) or tuple(sd["exp_avg"].shape) != tuple(self.exp_avg.shape):
+            other = "" if theirs is None else f" (its bucket holds {len(theirs)} tensors, e.g. `{(sorted(set(n for n, _ in theirs) - set(self.model.flat_offsets)) or [theirs[0][0]])[0]}`)"
+            raise ValueError(f"FusedAdamW.load_state_dict: this state dict was written for a different trainable set{other}: its moments are laid out for a bucket of "
+                             f"{sd['exp_avg'].numel()} elements, this model's bucket ({len(mine)} tensors, trainable= of its construction) has {self.exp_avg.numel()}")
         if "groups" in sd and len(sd["groups"]) != len(self.param_groups):
             raise ValueError(f"FusedAdamW.load_state_dict: the dict has {len(sd['groups'])} parameter groups, this optimizer {len(self.param_groups)}")
         self.step_count = int(sd["step"])

@@ -19,9 +19,72 @@ from .config import OwlConfig
 FREEZE_KEEP = ("layers.11", "box", "post_layernorm", "class_predictor", "queries")
 
 
-def is_trainable(name: str) -> bool:
-    """Literal restatement of the reference freeze rule (src/models.py:173-184)."""
-    return any(s in name for s in FREEZE_KEEP)
+def is_trainable(name: str, keep=FREEZE_KEEP) -> bool:
+    """Literal restatement of the reference freeze rule (src/models.py:173-184): a parameter is trainable iff any substring of `keep` occurs in
+    its name.  Substrings, not layer numbers: "layers.1" also selects layers 10 to 19, exactly as it would in the reference."""
+    return any(s in name for s in keep)
+
+
+# ---- units of the hand-written backward ------------------------------------------------------------------------------------
+# The backward computes gradients unit by unit (one kernel sequence per unit), so a trainable set is a set of whole units.  BUCKET_UNITS is also the
+# order of the units inside the flat bucket (encoder layers ascending where "layers" stands); the reference set keeps its historical layout.
+BUCKET_UNITS = ("queries", "layers", "backbone.post_layernorm", "post_post_layernorm", "class_predictor.dense0", "box_head",
+                "backbone.pre_layernorm", "backbone.embeddings")
+
+
+def unit_of(name: str):
+    """Unit a parameter belongs to: one of BUCKET_UNITS, or the index of its encoder layer."""
+    if name.startswith("backbone.encoder.layers."):
+        return int(name.split(".")[3])
+    for u in BUCKET_UNITS:
+        if name == u or name.startswith(u + "."):
+            return u
+    raise KeyError(name)
+
+
+def unit_label(u) -> str:
+    return f"backbone.encoder.layers.{u}" if isinstance(u, int) else u
+
+
+def trainable_units(cfg: OwlConfig, keep=None):
+    """The units selected by the substring list `keep` (None = the reference rule, FREEZE_KEEP), validated: a selection that takes part of a unit, or
+    nothing at all, raises ValueError.  -> (set of units, sorted tuple of trainable encoder layers)."""
+    keep = FREEZE_KEEP if keep is None else (keep if isinstance(keep, str) else tuple(keep))
+    if isinstance(keep, str) or any(not isinstance(s, str) for s in keep):
+        raise ValueError("trainable= takes an iterable of substrings of parameter names (the reference's freeze rule), e.g. "
+                         f"{FREEZE_KEEP!r}; got {keep!r}")
+    members = OrderedDict()
+    for n in param_shapes(cfg):
+        members.setdefault(unit_of(n), []).append(n)
+    units = set()
+    for u, names in members.items():
+        got = [n for n in names if is_trainable(n, keep)]
+        if got and len(got) != len(names):
+            missing = [n for n in names if n not in got]
+            raise ValueError(f"trainable={keep!r} selects part of the unit `{unit_label(u)}`: the backward trains a unit as a whole, and these of its "
+                             f"tensors are not selected: {missing}")
+        if got:
+            units.add(u)
+    if not units:
+        raise ValueError(f"trainable={keep!r} selects no parameter of the model (substrings of the reference's parameter names, e.g. {FREEZE_KEEP!r})")
+    return units, tuple(sorted(u for u in units if isinstance(u, int)))
+
+
+def backward_floor(units):
+    """The lowest point the backward's dX chain reaches for a set of units: "heads", "post_post_layernorm", "post_layernorm", a layer index,
+    "pre_layernorm" or "embeddings"."""
+    if "backbone.embeddings" in units:
+        return "embeddings"
+    if "backbone.pre_layernorm" in units:
+        return "pre_layernorm"
+    layers = [u for u in units if isinstance(u, int)]
+    if layers:
+        return min(layers)
+    if "backbone.post_layernorm" in units:
+        return "post_layernorm"
+    if "post_post_layernorm" in units:
+        return "post_post_layernorm"
+    return "heads"
 
 
 def param_shapes(cfg: OwlConfig) -> "OrderedDict[str, tuple]":
@@ -259,8 +322,8 @@ def patch_weight_gather_layout(w, patch_size: int):
     return full
 
 
-def count_trainable(cfg: OwlConfig) -> int:
-    return sum(int(np.prod(s)) for n, s in param_shapes(cfg).items() if is_trainable(n))
+def count_trainable(cfg: OwlConfig, keep=FREEZE_KEEP) -> int:
+    return sum(int(np.prod(s)) for n, s in param_shapes(cfg).items() if is_trainable(n, keep))
 
 
 # ---- text tower (query-bank initialisation, ref src/models.py:155-169) ------------------------------------------------
