@@ -431,7 +431,7 @@ __global__ __launch_bounds__(512) void class_sims_bwd_kernel(const float* __rest
         const float gc = __shfl(gcls, c < C ? c : 0, 64);
         if (lane < 32) G[r * 32 + lane] = f2bf((c < C && jc == lane) ? gc : 0.f);
         const float nrm = 1.0f / inv - 1e-6f;
-        coef_e = gs * inv / nrm;
+        coef_e = nrm > 0.f ? gs * inv / nrm : 0.f;               // an all-zero row gives nrm = 0 exactly: the norm's subgradient there is 0, not 0 / 0
     };
     auto body = [&](int64_t r, int jsel, float gcls, float coef_e) {
         for (int k4 = lane; k4 < (Dt >> 2); k4 += 64) {
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(512) void class_sims_bwd_pf_kernel(const float* __r
         const float gc = __shfl(gcls, c < C ? c : 0, 64);
         if (lane < 32) G[r * 32 + lane] = f2bf((c < C && jc == lane) ? gc : 0.f);
         const float nrm = 1.0f / inv - 1e-6f;
-        const float coef_e = gs * inv / nrm;
+        const float coef_e = nrm > 0.f ? gs * inv / nrm : 0.f;    // (class_sims_bwd_kernel's select: same bits)
 #pragma unroll
         for (int i = 0; i < NI; i++) {
             const int k4 = lane + 64 * i;

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void class_sims_wide_bwd_kernel(const float* _
         if (lane == 0) {
             const float nrm = 1.0f / inv - 1e-6f;
             s_inv[i] = inv;
-            s_coef[i] = i < nrows ? gs * inv / nrm : 0.f;
+            s_coef[i] = (i < nrows && nrm > 0.f) ? gs * inv / nrm : 0.f;    // (an all-zero row: nrm = 0 exactly; class_sims_bwd_kernel's select)
         }
     }
     f32x16 acc[NT];
