@@ -32,7 +32,7 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings).  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler).  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
 #define OWL_ABI_VERSION 8
 const char* owl_last_error(void);
@@ -189,6 +189,17 @@ int owl_bicubic_coeffs(int64_t in_size, int64_t out_size, int* bounds, int* kk, 
  * {src ptr, H, W, bounds_x ptr, kk_x ptr, ksize_x, bounds_y ptr, kk_y ptr, ksize_y, byte offset of its intermediate in tmp};
  * out [n_images,3,out_h,out_w]                                                                                        */
 int owl_preprocess_u8_batch(void* stream, const void* desc, int64_t n_images, int64_t max_h, unsigned char* tmp, const float* lut, void* out, int out_bf16, int64_t out_h, int64_t out_w);
+/* Train-time augmentation in the resampler (ABI 8, additive).  owl_bicubic_coeffs_box (HOST pointers): owl_bicubic_coeffs for the source box [in0, in1) of the axis
+ * (0 <= in0 < in1 <= in_size, float edges) = Pillow's precompute_coeffs under Image.resize(size, BICUBIC, box=...): scale = (in1 - in0) / out_size,
+ * center = in0 + (xx + 0.5) * scale, taps clipped to [0, in_size) (the image, not the box).  in0 = 0, in1 = in_size gives the bits of owl_bicubic_coeffs.  */
+int owl_bicubic_coeffs_box(int64_t in_size, double in0, double in1, int64_t out_size, int* bounds, int* kk, int64_t kk_capacity, int* ksize_out);
+/* owl_preprocess_u8_tiles (device pointers): one launch pair for a list of TILES, each one resample source box -> a cw x ch cell of output image b:
+ * desc = n_tiles x 18 int64 in DEVICE memory, per tile {src ptr, H, W, bounds_x ptr, kk_x ptr, ksize_x (tables of cw entries), bounds_y ptr, kk_y ptr,
+ * ksize_y (ch entries), y_first, n_rows (the source rows the vertical taps read: bounds_y[0] .. bounds_y[2ch-2] + bounds_y[2ch-1]), byte offset of its
+ * u8 [n_rows,cw,3] intermediate in tmp, b, x0, y0, cw, ch, flip}; writes out[b, :, y0 + y, x0 + (flip ? cw - 1 - x : x)] = lut[c][level], out
+ * [n_out,3,out_h,out_w] f32 | bf16.  max_rows = max n_rows.  The CALLER guarantees 0 <= b < n_out and that the cells of every output image lie inside it
+ * and cover it exactly (the descriptors live in device memory: preprocess.check_tile_cover is the host check).                                          */
+int owl_preprocess_u8_tiles(void* stream, const void* desc, int64_t n_tiles, int64_t max_rows, unsigned char* tmp, const float* lut, void* out, int out_bf16, int64_t n_out, int64_t out_h, int64_t out_w);
 /* images that already have the model's size (ABI 6): src u8 [n,H,W,3] (src_chw = 0) or [n,3,H,W] (src_chw = 1) -> lut -> out [n,3,H,W] f32 | bf16.  Pillow's resize
  * to the size an image already has is a copy, so this IS the reference pipeline for such images, bit for bit.  H*W % 4 == 0; src 4-byte, out 16-byte aligned.       */
 int owl_normalize_u8(void* stream, const unsigned char* src, int src_chw, const float* lut, void* out, int out_bf16, int64_t n_images, int64_t H, int64_t W);

@@ -82,6 +82,102 @@ OWL_API int owl_preprocess_u8_batch(void* stream, const void* desc, int64_t n_im
     return 0;
 }
 
+// ---- train-time augmentation: crop, flip and mosaic placement folded into the same two passes ----
+// A TILE is one resample: source box -> a cw x ch rectangle ("cell") of output image b.  The crop lives in the tap tables (owl_bicubic_coeffs_box: float box
+// edges, taps clipped to the image), the flip and the cell origin in the store address, so every source pixel is still interpolated once, Pillow-exact:
+// Image.resize((cw, ch), BICUBIC, box=...) [.transpose(FLIP_LEFT_RIGHT)] pasted at (x0, y0).  Like Pillow (Resample.c ImagingResample: ybox_first / ybox_last)
+// the horizontal pass runs only over the source rows [y_first, y_first + n_rows) that the vertical taps read; the intermediate is u8 [n_rows, cw, 3].
+// desc[i] = 18 int64 (device memory); the caller guarantees that the tiles of an output image cover it exactly (preprocess.py checks it on the host).
+struct TileDesc { const unsigned char* src; long long H, W; const int* bx; const int* kx; long long ksx; const int* by; const int* ky; long long ksy;
+                  long long y_first, n_rows, tmp_off, b, x0, y0, cw, ch, flip; };
+
+// A thread produces TILE_ROWS vertically adjacent pixels: a quarter of the workgroups (most of a mosaic's grid lies outside the small cells and only leaves
+// again), and in the horizontal pass one read of a column's weights serves four source rows.  Integer sums: the grouping cannot change a bit.
+// (Tried: gridDim.x workgroups per tile walking the tile's 256 x TILE_ROWS units, so that no workgroup starts without work -- slower at g = 1 and 2, equal
+// at g = 3, profiles/augment.md: the passes are bound by their byte loads per tap, not by the empty workgroups.)
+#define TILE_ROWS 4
+
+__global__ __launch_bounds__(256) void pp_tile_h_kernel(const TileDesc* __restrict__ desc, unsigned char* __restrict__ tmp_base) {
+    const TileDesc d = desc[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, r0 = blockIdx.y * TILE_ROWS;
+    if (x >= d.cw || r0 >= d.n_rows) return;
+    const int xmin = d.bx[2 * x], n = d.bx[2 * x + 1], last = (int)d.n_rows - 1;
+    const int* k = d.kx + (int64_t)x * d.ksx;
+    const unsigned char* row[TILE_ROWS];                       // rows past the range re-read the last one (in bounds) and are not stored
+    int acc[TILE_ROWS][3];
+#pragma unroll
+    for (int j = 0; j < TILE_ROWS; j++) {
+        row[j] = d.src + ((int64_t)(d.y_first + min(r0 + j, last)) * d.W + xmin) * 3;
+        acc[j][0] = acc[j][1] = acc[j][2] = 1 << (PIL_PRECISION_BITS - 1);
+    }
+    for (int t = 0; t < n; t++) {
+        const int w = k[t];
+#pragma unroll
+        for (int j = 0; j < TILE_ROWS; j++) {
+            acc[j][0] += (int)row[j][3 * t] * w;
+            acc[j][1] += (int)row[j][3 * t + 1] * w;
+            acc[j][2] += (int)row[j][3 * t + 2] * w;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < TILE_ROWS; j++) {
+        if (r0 + j > last) break;
+        unsigned char* o = tmp_base + d.tmp_off + ((int64_t)(r0 + j) * d.cw + x) * 3;
+        o[0] = pil_clip8(acc[j][0]); o[1] = pil_clip8(acc[j][1]); o[2] = pil_clip8(acc[j][2]);
+    }
+}
+
+template <bool BF16>
+__global__ __launch_bounds__(256) void pp_tile_v_kernel(const TileDesc* __restrict__ desc, const unsigned char* __restrict__ tmp_base,
+                                                        void* __restrict__ out, const float* __restrict__ lut, int out_h, int out_w) {
+    const TileDesc d = desc[blockIdx.z];
+    const int x = blockIdx.x * 256 + threadIdx.x, y0 = blockIdx.y * TILE_ROWS;
+    if (x >= d.cw || y0 >= d.ch) return;
+    const int64_t stride = d.cw * 3, plane = (int64_t)out_h * out_w;
+    const int ox = (int)d.x0 + (d.flip ? (int)d.cw - 1 - x : x);
+    for (int y = y0; y < min(y0 + TILE_ROWS, (int)d.ch); y++) {
+        const int ymin = d.by[2 * y] - (int)d.y_first, n = d.by[2 * y + 1];
+        const int* k = d.ky + (int64_t)y * d.ksy;
+        const unsigned char* col = tmp_base + d.tmp_off + (int64_t)ymin * stride + x * 3;
+        int s0 = 1 << (PIL_PRECISION_BITS - 1), s1 = s0, s2 = s0;
+        for (int t = 0; t < n; t++) {
+            const int w = k[t];
+            s0 += (int)col[t * stride] * w;
+            s1 += (int)col[t * stride + 1] * w;
+            s2 += (int)col[t * stride + 2] * w;
+        }
+        const float v0 = lut[pil_clip8(s0)], v1 = lut[256 + pil_clip8(s1)], v2 = lut[512 + pil_clip8(s2)];
+        const int64_t o = d.b * 3 * plane + (d.y0 + y) * out_w + ox;
+        if (BF16) {
+            bf16_t* p = (bf16_t*)out;
+            p[o] = f2bf(v0); p[plane + o] = f2bf(v1); p[2 * plane + o] = f2bf(v2);
+        } else {
+            float* p = (float*)out;
+            p[o] = v0; p[plane + o] = v1; p[2 * plane + o] = v2;
+        }
+    }
+}
+
+// max_rows = the largest n_rows of the list (the horizontal grid's height); out [n_out, 3, out_h, out_w].  A cell is at most the canvas, so the grids are
+// sized by out_w x max_rows and out_w x out_h pixels per tile (TILE_ROWS rows per workgroup) and the workgroups outside a tile's cell leave at once.
+OWL_API int owl_preprocess_u8_tiles(void* stream, const void* desc, int64_t n_tiles, int64_t max_rows, unsigned char* tmp, const float* lut,
+                                    void* out, int out_bf16, int64_t n_out, int64_t out_h, int64_t out_w) {
+    OWL_CHECK_ARG(desc && tmp && lut && out, "owl_preprocess_u8_tiles: null pointer");
+    OWL_CHECK_ARG(n_tiles > 0 && n_tiles < 65536 && max_rows > 0 && max_rows < 65536 && n_out > 0 && n_out <= n_tiles && out_h > 0 && out_h < 65536 && out_w > 0 && out_w < 65536,
+                  "owl_preprocess_u8_tiles: bad sizes tiles=%lld max_rows=%lld n_out=%lld out=%lldx%lld", (long long)n_tiles, (long long)max_rows, (long long)n_out,
+                  (long long)out_h, (long long)out_w);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned gx = (unsigned)((out_w + 255) / 256), gy = (unsigned)((out_h + TILE_ROWS - 1) / TILE_ROWS);
+    hipLaunchKernelGGL(pp_tile_h_kernel, dim3(gx, (unsigned)((max_rows + TILE_ROWS - 1) / TILE_ROWS), (unsigned)n_tiles), dim3(256), 0, s, (const TileDesc*)desc, tmp);
+    OWL_LAUNCH_CHECK();
+    if (out_bf16)
+        hipLaunchKernelGGL((pp_tile_v_kernel<true>), dim3(gx, gy, (unsigned)n_tiles), dim3(256), 0, s, (const TileDesc*)desc, tmp, out, lut, (int)out_h, (int)out_w);
+    else
+        hipLaunchKernelGGL((pp_tile_v_kernel<false>), dim3(gx, gy, (unsigned)n_tiles), dim3(256), 0, s, (const TileDesc*)desc, tmp, out, lut, (int)out_h, (int)out_w);
+    OWL_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- images that already have the model's size (a dataset that resizes on the host, or synthetic u8 pixels): only the table step is left ----
 // src u8 [B,H,W,3] (HWC, what PIL / a DataLoader of raw images hands over) or [B,3,H,W] (CHW) -> out [B,3,H,W] f32 | bf16 = lut[c][level].
 // Pillow's resize to the size an image already has returns a copy (Image.resize: `if self.size == size and box == (0, 0) + self.size: return self.copy()`),

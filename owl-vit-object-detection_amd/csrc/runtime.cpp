@@ -33,28 +33,25 @@ static inline double pil_bicubic(double x) {
     return 0.0;
 }
 
-// bounds[2*out] = {first tap, tap count}; kk[out*ksize] fixed-point weights (zero padded).  HOST pointers.
-OWL_API int owl_bicubic_coeffs(int64_t in_size, int64_t out_size, int* bounds, int* kk, int64_t kk_capacity, int* ksize_out) {
-    if (in_size <= 0 || out_size <= 0 || !bounds || !kk || !ksize_out) {
-        owl_set_error("owl_bicubic_coeffs: bad arguments (in=%lld out=%lld)", (long long)in_size, (long long)out_size);
-        return -1;
-    }
+// Pillow's precompute_coeffs for one axis and a source box [in0, in1) (Image.resize(size, BICUBIC, box=...)): the taps are clipped to the IMAGE
+// [0, in_size), not to the box.  in0 = 0, in1 = in_size is the whole-axis resize: x - 0.0 and 0.0 + x are exact, so both entries share this body bit for bit.
+static int bicubic_coeffs_impl(const char* who, int64_t in_size, double in0, double in1, int64_t out_size, int* bounds, int* kk, int64_t kk_capacity, int* ksize_out) {
     const int PRECISION_BITS = 32 - 8 - 2;
     double scale, filterscale;
-    filterscale = scale = (double)in_size / (double)out_size;
+    filterscale = scale = (in1 - in0) / (double)out_size;
     if (filterscale < 1.0) filterscale = 1.0;
     const double support = 2.0 * filterscale;
     const int ksize = (int)ceil(support) * 2 + 1;
     if ((int64_t)ksize * out_size > kk_capacity) {
-        owl_set_error("owl_bicubic_coeffs: kk capacity %lld < %lld", (long long)kk_capacity, (long long)ksize * out_size);
+        owl_set_error("%s: kk capacity %lld < %lld", who, (long long)kk_capacity, (long long)ksize * out_size);
         return -1;
     }
     *ksize_out = ksize;
     const double ss = 1.0 / filterscale;
     double w[4096];
-    if (ksize > 4096) { owl_set_error("owl_bicubic_coeffs: ksize %d too large", ksize); return -1; }
+    if (ksize > 4096) { owl_set_error("%s: ksize %d too large", who, ksize); return -1; }
     for (int64_t xx = 0; xx < out_size; xx++) {
-        const double center = (xx + 0.5) * scale;
+        const double center = in0 + (xx + 0.5) * scale;
         int xmin = (int)(center - support + 0.5);
         if (xmin < 0) xmin = 0;
         int xmax = (int)(center + support + 0.5);
@@ -76,6 +73,24 @@ OWL_API int owl_bicubic_coeffs(int64_t in_size, int64_t out_size, int* bounds, i
         bounds[2 * xx + 1] = xmax;
     }
     return 0;
+}
+
+// bounds[2*out] = {first tap, tap count}; kk[out*ksize] fixed-point weights (zero padded).  HOST pointers.
+OWL_API int owl_bicubic_coeffs(int64_t in_size, int64_t out_size, int* bounds, int* kk, int64_t kk_capacity, int* ksize_out) {
+    if (in_size <= 0 || out_size <= 0 || !bounds || !kk || !ksize_out) {
+        owl_set_error("owl_bicubic_coeffs: bad arguments (in=%lld out=%lld)", (long long)in_size, (long long)out_size);
+        return -1;
+    }
+    return bicubic_coeffs_impl("owl_bicubic_coeffs", in_size, 0.0, (double)in_size, out_size, bounds, kk, kk_capacity, ksize_out);
+}
+
+// The same tables for the source box [in0, in1) of an axis of in_size pixels (float edges; 0 <= in0 < in1 <= in_size): a crop folded into the resize.
+OWL_API int owl_bicubic_coeffs_box(int64_t in_size, double in0, double in1, int64_t out_size, int* bounds, int* kk, int64_t kk_capacity, int* ksize_out) {
+    if (in_size <= 0 || in_size > INT32_MAX || out_size <= 0 || !bounds || !kk || !ksize_out || !(in0 >= 0.0) || !(in1 > in0) || !(in1 <= (double)in_size)) {
+        owl_set_error("owl_bicubic_coeffs_box: bad arguments (in=%lld box=[%g, %g) out=%lld)", (long long)in_size, in0, in1, (long long)out_size);
+        return -1;
+    }
+    return bicubic_coeffs_impl("owl_bicubic_coeffs_box", in_size, in0, in1, out_size, bounds, kk, kk_capacity, ksize_out);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

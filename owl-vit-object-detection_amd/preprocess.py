@@ -85,6 +85,32 @@ class DeviceImageProcessor:
         self._keep = (imgs, desc_d)          # keep the sources alive until the stream has consumed them
         return {"pixel_values": out}
 
+    def run_tiles(self, desc_d: torch.Tensor, n_tiles: int, max_rows: int, tmp_bytes: int, n_out: int) -> torch.Tensor:
+        """Launch owl_preprocess_u8_tiles on the current stream for descriptors that are already on the device with absolute addresses (`build_tile_tables` +
+        `resolve_tile_descs`) and whose cover the caller has checked (`check_tile_cover`) -> [n_out,3,S,S] self.dtype."""
+        if self._tmp is None or self._tmp.numel() < tmp_bytes:
+            self._tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=self.device)
+        out = torch.empty(n_out, 3, self.size, self.size, dtype=self.dtype, device=self.device)
+        _lib.call("owl_preprocess_u8_tiles", ops.stream(), desc_d, n_tiles, max_rows, self._tmp, self.lut, out,
+                  1 if self.dtype == torch.bfloat16 else 0, n_out, self.size, self.size)
+        return out
+
+    def tiles(self, images, tiles, n_out: int) -> torch.Tensor:
+        """The augmenting form of __call__: every `Tile` resamples a source box of `images[tile.src]` into a cell of output image `tile.b`, flipped or not --
+        Pillow's `resize((cw, ch), BICUBIC, box=...)`, `transpose(FLIP_LEFT_RIGHT)` and `paste`, bit for bit, in one launch pair.  Raises ValueError unless
+        the cells of every output image cover it exactly."""
+        imgs = [self._to_device(im) for im in images]
+        shapes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
+        tiles = list(tiles)
+        check_tile_cover(tiles, n_out, self.size, shapes)
+        desc, arena, tmp_bytes, max_rows = build_tile_tables(shapes, tiles)
+        arena_d = torch.from_numpy(arena).to(self.device, non_blocking=True)
+        resolve_tile_descs(desc, [im.data_ptr() for im in imgs], arena_d.data_ptr())
+        desc_d = torch.from_numpy(desc).to(self.device, non_blocking=True)
+        out = self.run_tiles(desc_d, len(tiles), max_rows, tmp_bytes, n_out)
+        self._keep = (imgs, arena_d, desc_d)          # keep the sources and tables alive until the stream has consumed them
+        return out
+
     def normalize_sized(self, src_u8: torch.Tensor, chw: bool) -> torch.Tensor:
         """Images that already have the model's size: u8 [B,S,S,3] (chw=False) or [B,3,S,S] (chw=True) ON THE DEVICE -> [B,3,S,S] self.dtype.  Pillow's resize to
         the size an image already has is a copy, so only the table step of the reference pipeline is left (owl_normalize_u8)."""
@@ -98,6 +124,251 @@ class DeviceImageProcessor:
         out = torch.empty(n, 3, self.size, self.size, dtype=self.dtype, device=self.device)
         _lib.call("owl_normalize_u8", ops.stream(), src_u8, 1 if chw else 0, self.lut, out, 1 if self.dtype == torch.bfloat16 else 0, n, H, W_)
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Train-time augmentation (random crop, horizontal flip, mosaic) folded into the device resampler.  Every augmentation that changes scale is a
+# resample, and a g x g mosaic needs g^2 of them per output image: done in DataLoader workers that is exactly the CPU work the device resize took
+# off the host.  Here the host only draws the parameters and builds Pillow's tap tables for the crop boxes (`owl_bicubic_coeffs_box`); crop, flip and
+# placement ride in the two resize passes (`owl_preprocess_u8_tiles`), one interpolation per source pixel, bit-exact against
+# `Image.resize(cell, BICUBIC, box=crop)` / `transpose(FLIP_LEFT_RIGHT)` / `paste`.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+from collections import namedtuple
+
+# one resample: the box (left, upper, right, lower -- float pixel edges, as Pillow's `box=`) of source image `src` -> the cw x ch cell at (x0, y0) of output
+# image `b`, mirrored left-right if `flip`
+Tile = namedtuple("Tile", "src box flip b x0 y0 cw ch")
+
+TILE_DESC_WORDS = 18           # int64 words per tile descriptor (csrc/preprocess.hip: struct TileDesc)
+
+
+def check_tile_cover(tiles, n_out: int, size: int, shapes=None):
+    """Raises ValueError unless the cells of every output image 0..n_out-1 lie inside the size x size canvas, do not overlap and cover it -- the kernels write
+    each output pixel from exactly one tile and leave no pixel unwritten only then -- and (given the sources' (H, W) `shapes`) every box lies inside its source."""
+    if not tiles:
+        raise ValueError("tiles: empty tile list")
+    a = np.asarray([(t.b, t.x0, t.y0, t.cw, t.ch) for t in tiles], dtype=np.int64)
+    b, x0, y0, cw, ch = a.T
+    if (b < 0).any() or (b >= n_out).any():
+        raise ValueError(f"tiles: output index outside [0, {n_out})")
+    if (cw <= 0).any() or (ch <= 0).any() or (x0 < 0).any() or (y0 < 0).any() or (x0 + cw > size).any() or (y0 + ch > size).any():
+        raise ValueError(f"tiles: a cell lies outside the {size} x {size} canvas")
+    area = np.bincount(b, weights=(cw * ch).astype(np.float64), minlength=n_out)
+    if (area != float(size * size)).any():
+        raise ValueError(f"tiles: the cells of output image {int(np.flatnonzero(area != float(size * size))[0])} do not cover the canvas exactly")
+    for i in range(n_out):                                   # inside + total area = canvas: an exact cover unless two cells overlap
+        m = np.flatnonzero(b == i)
+        if m.size > 1:
+            ox = (x0[m, None] < (x0 + cw)[None, m]) & (x0[None, m] < (x0 + cw)[m, None])
+            oy = (y0[m, None] < (y0 + ch)[None, m]) & (y0[None, m] < (y0 + ch)[m, None])
+            if int((ox & oy).sum()) != m.size:               # (every cell overlaps itself)
+                raise ValueError(f"tiles: cells of output image {i} overlap")
+    if shapes is not None:
+        src = np.asarray([t.src for t in tiles], dtype=np.int64)
+        if (src < 0).any() or (src >= len(shapes)).any():
+            raise ValueError(f"tiles: source index outside the batch of {len(shapes)}")
+        hw = np.asarray(shapes, dtype=np.float64).reshape(-1, 2)[src]
+        l, u, r, lo = np.asarray([t.box for t in tiles], dtype=np.float64).reshape(-1, 4).T
+        bad = ~((0.0 <= l) & (l < r) & (r <= hw[:, 1]) & (0.0 <= u) & (u < lo) & (lo <= hw[:, 0]))           # (written so that a NaN edge fails)
+        if bad.any():
+            t = tiles[int(np.flatnonzero(bad)[0])]
+            raise ValueError(f"tiles: box {tuple(t.box)} is empty or outside its {shapes[t.src][1]} x {shapes[t.src][0]} source")
+
+
+def _ksize(extent: float, out: int) -> int:
+    return int(math.ceil(2.0 * max(extent / out, 1.0))) * 2 + 1          # Pillow's ksize for the bicubic filter (support 2)
+
+
+def _table_calls(jobs):
+    """jobs: (in_size, in0, in1, out_size, bounds address, kk address, kk capacity, expected ksize).  ctypes releases the GIL for the duration of each call."""
+    fn = _lib.load().owl_bicubic_coeffs_box
+    got = np.zeros(1, dtype=np.int32)
+    pgot = got.ctypes.data
+    for n_in, in0, in1, n_out, pb, pk, cap, ks in jobs:
+        if fn(n_in, in0, in1, n_out, pb, pk, cap, pgot) != 0:
+            raise _lib.OwlLibError(f"owl_bicubic_coeffs_box failed: {_lib.last_error()}")
+        assert got[0] == ks
+
+
+def build_tile_tables(shapes, tiles):
+    """Host half of the tile path: Pillow's tap tables of every tile's two axes (`owl_bicubic_coeffs_box`), packed in one int32 arena, and the descriptors with
+    RELATIVE addresses -- source = index into the batch, tables = byte offsets into the arena -- because the device addresses exist only once the staging slab
+    has been allocated (`resolve_tile_descs`).  -> (desc int64 [n,18], arena int32, tmp bytes, max rows)."""
+    n = len(tiles)
+    hw = np.asarray([shapes[t.src] for t in tiles], dtype=np.int64).reshape(n, 2)
+    box = np.asarray([t.box for t in tiles], dtype=np.float64).reshape(n, 4)
+    cw = np.asarray([t.cw for t in tiles], dtype=np.int64)
+    ch = np.asarray([t.ch for t in tiles], dtype=np.int64)
+    ksx = np.asarray([_ksize(b[2] - b[0], w) for b, w in zip(box.tolist(), cw.tolist())], dtype=np.int64)
+    ksy = np.asarray([_ksize(b[3] - b[1], h) for b, h in zip(box.tolist(), ch.tolist())], dtype=np.int64)
+    sizes = np.stack([2 * cw, cw * ksx, 2 * ch, ch * ksy], axis=1)                  # ints of bx, kx, by, ky per tile
+    ends = np.cumsum(sizes.reshape(-1)).reshape(n, 4)
+    offs = ends - sizes                                                             # int32 offsets into the arena
+    arena = np.zeros(int(ends[-1, -1]), dtype=np.int32)
+    addr = arena.ctypes.data + 4 * offs
+    jobs = []
+    for i in range(n):
+        H, W = hw[i].tolist()
+        l, u, r, lo = box[i].tolist()
+        pbx, pkx, pby, pky = addr[i].tolist()
+        jobs.append((W, l, r, int(cw[i]), pbx, pkx, int(sizes[i, 1]), int(ksx[i])))
+        jobs.append((H, u, lo, int(ch[i]), pby, pky, int(sizes[i, 3]), int(ksy[i])))
+    _table_calls(jobs)
+    y_first = arena[offs[:, 2]].astype(np.int64)
+    n_rows = arena[offs[:, 2] + 2 * ch - 2].astype(np.int64) + arena[offs[:, 2] + 2 * ch - 1] - y_first
+    tmp_sizes = (n_rows * cw * 3 + 255) // 256 * 256
+    desc = np.zeros((n, TILE_DESC_WORDS), dtype=np.int64)
+    desc[:, 0] = [t.src for t in tiles]
+    desc[:, 1:3] = hw
+    desc[:, 3], desc[:, 4], desc[:, 5] = 4 * offs[:, 0], 4 * offs[:, 1], ksx
+    desc[:, 6], desc[:, 7], desc[:, 8] = 4 * offs[:, 2], 4 * offs[:, 3], ksy
+    desc[:, 9], desc[:, 10], desc[:, 11] = y_first, n_rows, np.cumsum(tmp_sizes) - tmp_sizes
+    desc[:, 12] = [t.b for t in tiles]
+    desc[:, 13] = [t.x0 for t in tiles]
+    desc[:, 14] = [t.y0 for t in tiles]
+    desc[:, 15], desc[:, 16] = cw, ch
+    desc[:, 17] = [1 if t.flip else 0 for t in tiles]
+    return desc, arena, int(tmp_sizes.sum()), int(n_rows.max())
+
+
+def resolve_tile_descs(desc: np.ndarray, src_ptrs, arena_ptr: int):
+    """In place: source indices -> device addresses of the sources, arena offsets -> device addresses of the tables."""
+    desc[:, 0] = np.asarray(src_ptrs, dtype=np.int64)[desc[:, 0]]
+    desc[:, [3, 4, 6, 7]] += np.int64(arena_ptr)
+
+
+def transform_boxes(boxes_xywh, labels, crop, flip, cell, size, min_visibility=0.3, min_box=2.0, drop=True, return_mask=False):
+    """COCO `xywh` pixel boxes of a source -> the boxes of its tile, float64 numpy on the host: intersect with the crop (left, upper, right, lower); drop a box
+    whose visible area / original area < `min_visibility` or one of whose visible sides, measured in canvas pixels, is below `min_box`; map into the cell
+    (x0, y0, cw, ch) of the size x size canvas, mirrored about the cell's vertical axis under `flip`.  -> (normalised xyxy in [0, 1] float32 [k,4], labels [k])
+    -- the form `train_util.coco_to_model_input` returns.  `crop`, `flip` and `cell` are one tile's, or arrays with a row per box (the boxes of several tiles
+    in one call).  drop=False keeps every box with a non-empty intersection (the sampler's last resort); return_mask=True appends the mask of kept boxes."""
+    bx = np.asarray(boxes_xywh, dtype=np.float64).reshape(-1, 4)
+    lb = np.asarray(labels).reshape(-1)
+    c = np.asarray(crop, dtype=np.float64)
+    l, u, r, lo = c[..., 0], c[..., 1], c[..., 2], c[..., 3]
+    ce = np.asarray(cell, dtype=np.float64)
+    cx0, cy0, cw, ch = ce[..., 0], ce[..., 1], ce[..., 2], ce[..., 3]
+    x1, y1, x2, y2 = bx[:, 0], bx[:, 1], bx[:, 0] + bx[:, 2], bx[:, 1] + bx[:, 3]
+    ix1, iy1, ix2, iy2 = np.maximum(x1, l), np.maximum(y1, u), np.minimum(x2, r), np.minimum(y2, lo)
+    vw, vh = np.maximum(ix2 - ix1, 0.0), np.maximum(iy2 - iy1, 0.0)
+    sx, sy = cw / (r - l), ch / (lo - u)                       # canvas pixels per source pixel
+    keep = (vw > 0.0) & (vh > 0.0)
+    if drop:
+        area = bx[:, 2] * bx[:, 3]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            keep &= ~((vw * vh) / area < min_visibility) & (area > 0.0)
+        keep &= ~(vw * sx < min_box) & ~(vh * sy < min_box)
+    ux1, ux2 = (ix1 - l) * sx, (ix2 - l) * sx
+    f = np.asarray(flip, dtype=bool)
+    ux1, ux2 = np.where(f, cw - ux2, ux1), np.where(f, cw - ux1, ux2)
+    out = np.stack([(cx0 + ux1) / size, (cy0 + (iy1 - u) * sy) / size, (cx0 + ux2) / size, (cy0 + (iy2 - u) * sy) / size], axis=1)
+    res = (np.clip(out[keep], 0.0, 1.0).astype(np.float32), lb[keep])
+    return res + (keep,) if return_mask else res
+
+
+class TrainAugment:
+    """Deterministic host-side sampler of train-time crops, flips and mosaics, plus the box transform; the pixels are produced on the device by
+    `DevicePrefetcher(..., augment=TrainAugment(size))` (or `DeviceImageProcessor.tiles`).
+
+    Per output image `j` of a batch it draws a grid `g` from `mosaic` (g x g cells of size/g pixels; `size % g == 0`), and per cell a source image of the
+    same batch (cell 0: image `j` itself; the others without replacement among the other images where the batch has enough, with replacement otherwise), a crop
+    box -- area fraction uniform in `scale`, aspect log-uniform in `ratio` RELATIVE to the source's own aspect (the plain pipeline already maps every image to
+    a square), placed uniformly inside the image, float edges rounded to float32 (what Pillow's `box=` holds) -- and a flip with probability `hflip`.
+    All draws of batch `index` of epoch `epoch` come from `numpy.random.default_rng((seed, rank, epoch, index))`: the same key gives the same batch bit for bit,
+    ranks differ, nothing depends on thread timing.
+
+    Targets: `sample` takes the sources' COCO `xywh` PIXEL boxes and returns, per output image, NORMALISED `xyxy` float32 boxes in [0, 1] and their labels
+    (`transform_boxes`) -- the form `coco_to_model_input` returns, so the caller SKIPS that function for augmented batches.  `PackedTargets` needs at least one
+    box per image: an output image left without one is redrawn up to `max_tries` times, then falls back to its whole, unflipped source at g = 1 with every box
+    kept; `fallbacks` counts those."""
+
+    def __init__(self, size, *, mosaic=(1,), scale=(0.3, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, min_visibility=0.3, min_box=2.0, seed=0, rank=0, max_tries=10):
+        self.size = int(size)
+        self.mosaic = tuple(int(g) for g in mosaic)
+        if not self.mosaic or any(g < 1 or self.size % g for g in self.mosaic):
+            raise ValueError(f"TrainAugment: every mosaic grid must be >= 1 and divide size = {self.size}, got {mosaic}")
+        self.scale = (float(scale[0]), float(scale[1]))
+        self.ratio = (float(ratio[0]), float(ratio[1]))
+        if not 0.0 < self.scale[0] <= self.scale[1] <= 1.0 or not 0.0 < self.ratio[0] <= self.ratio[1]:
+            raise ValueError("TrainAugment: need 0 < scale[0] <= scale[1] <= 1 and 0 < ratio[0] <= ratio[1]")
+        self.hflip = float(hflip)
+        self.min_visibility = float(min_visibility)
+        self.min_box = float(min_box)
+        self.seed, self.rank, self.max_tries = int(seed), int(rank), int(max_tries)
+        self.fallbacks = 0
+
+    def _crops(self, rng, H, W):
+        """One crop per entry of the float64 arrays H, W -> [n,4] (left, upper, right, lower)."""
+        n = len(H)
+        area = rng.uniform(self.scale[0], self.scale[1], n)
+        r = np.exp(rng.uniform(math.log(self.ratio[0]), math.log(self.ratio[1]), n))
+        w, h = np.minimum(W * np.sqrt(area * r), W), np.minimum(H * np.sqrt(area / r), H)
+        l, u = rng.uniform(0.0, 1.0, n) * (W - w), rng.uniform(0.0, 1.0, n) * (H - h)
+        box = np.stack([l, u, l + w, u + h], axis=1).astype(np.float32).astype(np.float64)
+        box[:, 2], box[:, 3] = np.minimum(box[:, 2], W), np.minimum(box[:, 3], H)         # (float32 rounding may step over the border)
+        bad = (box[:, 2] - box[:, 0] < 1.0) | (box[:, 3] - box[:, 1] < 1.0)                # an image too small for the draw: take it whole
+        box[bad] = np.stack([0.0 * W, 0.0 * H, W, H], axis=1)[bad]
+        return box
+
+    def _draw(self, rng, J, hw, allb, alll, first, count):
+        """One draw for each output image of the index array J, vectorised over all their cells -> per-tile arrays (output image, source, box [T,4], flip,
+        cell [T,4]) and the surviving targets (output image of each, boxes, labels), ordered by output image, then cell, then source box."""
+        B, S = len(hw), self.size
+        g = np.asarray(self.mosaic, dtype=np.int64)[rng.integers(len(self.mosaic), size=len(J))]
+        n = g * g
+        T = int(n.sum())
+        row = np.repeat(np.arange(len(J)), n)                                    # which entry of J a tile belongs to
+        q = np.arange(T) - np.repeat(np.cumsum(n) - n, n)                       # its cell within the grid
+        out = J[row]
+        # sources: cell 0 is the image itself; the others walk a random order of the other images (no repeats) where the batch has enough of them
+        order = np.argsort(rng.random((len(J), max(B - 1, 1))), axis=1)
+        others = order + (order >= J[:, None])
+        src = np.where(q == 0, out, others[row, np.minimum(np.maximum(q - 1, 0), max(B - 2, 0))]) if B > 1 else out.copy()
+        again = rng.integers(B, size=T)
+        short = (np.repeat(n, n) - 1 > B - 1) & (q > 0)                         # a grid with more cells than the batch has other images: with replacement
+        src = np.where(short, again, src)
+        box = self._crops(rng, hw[src, 0], hw[src, 1])
+        flip = rng.random(T) < self.hflip
+        c = S // np.repeat(g, n)
+        cell = np.stack([(q % np.repeat(g, n)) * c, (q // np.repeat(g, n)) * c, c, c], axis=1)
+        cnt = count[src]
+        per = np.repeat(np.arange(T), cnt)                                       # the tile of every candidate box
+        idx = first[src][per] + np.arange(len(per)) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        keep_b, keep_l, kept = transform_boxes(allb[idx], alll[idx], box[per], flip[per], cell[per], S, self.min_visibility, self.min_box, return_mask=True)
+        return out, src, box, flip, cell, out[per][kept], keep_b, keep_l
+
+    def sample(self, shapes, boxes, labels, epoch, index):
+        """shapes: the batch's (H, W); boxes / labels: per source image [n,4] COCO xywh pixels / [n].  -> (tiles, boxes, labels): the `Tile`s of the whole batch
+        (output image j = tiles with b == j, in cell order) and per output image normalised xyxy float32 [k,4] / labels [k], k >= 1."""
+        rng = np.random.default_rng((self.seed, self.rank, int(epoch), int(index)))
+        B, S = len(shapes), self.size
+        hw = np.asarray(shapes, dtype=np.float64).reshape(B, 2)
+        boxes = [np.asarray(b, dtype=np.float64).reshape(-1, 4) for b in boxes]
+        labels = [np.asarray(l).reshape(-1) for l in labels]
+        allb, alll = np.concatenate(boxes), np.concatenate(labels)
+        count = np.asarray([len(b) for b in boxes], dtype=np.int64)
+        first = np.cumsum(count) - count
+        tiles, out_b, out_l = [None] * B, [None] * B, [None] * B
+        J = np.arange(B)
+        for _ in range(self.max_tries):                                          # images left without a box are drawn again
+            out, src, box, flip, cell, owner, kb, kl = self._draw(rng, J, hw, allb, alll, first, count)
+            have = np.bincount(owner, minlength=B)
+            for j in J[have[J] > 0].tolist():
+                m = out == j
+                tiles[j] = [Tile(k, tuple(bq), f, j, *cq) for k, bq, f, cq in zip(src[m].tolist(), box[m].tolist(), flip[m].tolist(), cell[m].tolist())]
+                out_b[j], out_l[j] = kb[owner == j], kl[owner == j]
+            J = J[have[J] == 0]
+            if not len(J):
+                break
+        for j in J.tolist():                                                      # last resort: the whole, unflipped source at g = 1, every box kept
+            H, W = shapes[j]
+            tiles[j] = [Tile(j, (0.0, 0.0, float(W), float(H)), False, j, 0, 0, S, S)]
+            out_b[j], out_l[j] = transform_boxes(boxes[j], labels[j], tiles[j][0].box, False, (0, 0, S, S), S, drop=False)
+            if not len(out_b[j]):
+                raise ValueError(f"TrainAugment: image {j} of batch {index} has no box inside the image (every image needs at least one target)")
+            self.fallbacks += 1
+        return [t for ts in tiles for t in ts], out_b, out_l
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -190,14 +461,20 @@ class DevicePrefetcher:
     (the reference's `metadata`) and everything else pass through untouched.  The reference loop's own `.to(device)` calls become no-ops.
 
     Ordering: the consumer's stream waits for the batch's event and the tensors are `record_stream`-ed on it, so the caching allocator does not recycle them
-    while the step still reads them; a pinned slab is reused only after its own copy has completed.  `threaded=True` pulls from the loader, stages and
+    while the step still reads them; a pinned slab is reused only after its own copy has completed.
+
+    `augment=TrainAugment(size)` (train loops only; eval never augments) turns on random crops, flips and mosaics: the loader must then yield
+    `(images, labels, boxes, *rest)` with uint8 HWC images, per-image label tensors and per-image COCO `xywh` PIXEL boxes.  The staging thread draws the
+    batch's tiles (keyed by the augment's seed and rank, `set_epoch`'s epoch and the batch's index), builds their tap tables and descriptors, ships them in
+    the same slab as the pixels and runs `owl_preprocess_u8_tiles` on the copy stream; it hands over `(pixel_values, labels, boxes, *rest)` with the boxes
+    already NORMALISED `xyxy` (skip `coco_to_model_input` for such batches).  `target_transform` then sees the augmented targets.  `threaded=True` pulls from the loader, stages and
     enqueues from a background thread (`depth` batches ahead); `threaded=False` does the same work inside `__next__`, one batch ahead.
     No CPU fallback: images are processed by libowlhip.so on the device or not at all."""
 
     _END = object()
 
     def __init__(self, loader, device="cuda", size=768, dtype=torch.bfloat16, depth=2, processor=None, target_transform=None,
-                 move_targets=True, threaded=True):
+                 move_targets=True, threaded=True, augment=None):
         self.loader = loader
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -223,16 +500,28 @@ class DevicePrefetcher:
         self.bytes_h2d = 0                 # bytes sent over the bus so far (statistics: bench.py reports bytes per image)
         self.batches = 0
         self.stage_seconds = 0.0           # host time spent staging (pull from the loader excluded): must stay below the step time for the stage to hide
+        self.augment = augment
+        if augment is not None and augment.size != self.size:
+            raise ValueError(f"DevicePrefetcher: augment.size = {augment.size} but size = {self.size}")
+        self.augment_seconds = 0.0         # of which: drawing the tiles and building their tap tables and descriptors
+        self._epoch = 0
+        self._index = 0                    # index of the next batch within the epoch (reset by __iter__)
+
+    def set_epoch(self, epoch: int):
+        """The epoch that keys the augmentation's draws (as DistributedSampler.set_epoch: call it before iterating)."""
+        self._epoch = int(epoch)
 
     def __len__(self):
         return len(self.loader)
 
     # -- staging (runs in the background thread when threaded) ------------------------------------------------------------------------------
-    def _h2d(self, items):
+    def _h2d(self, items, patch=None):
         """Host tensors (the batch's images AND its target tensors) -> ONE pinned ring slab -> ONE H2D copy -> device views (never one small copy per tensor: a
         pageable source makes every `.to(device)` a blocking round trip).  A large tensor the caller already pinned (DataLoader(pin_memory=True)) goes as it is.
         The host-side copy into the slab is a plain memmove (ctypes: releases the GIL): torch's own CPU copy fans out over the intra-op thread pool, which --
-        called from a second thread on a many-core host -- costs several times the copy itself (measured: 40 ms per 57 MB batch on the 256-thread GPU box)."""
+        called from a second thread on a many-core host -- costs several times the copy itself (measured: 40 ms per 57 MB batch on the 256-thread GPU box).
+        `patch(out)` runs once every item's device address is known and before the host bytes are copied into the slab: the tile descriptors, which ride
+        in this slab, hold device addresses of other items of it."""
         import ctypes
         while self._inflight and self._inflight[0][0].query():          # caller-pinned sources whose copies have completed
             self._inflight.popleft()
@@ -255,17 +544,21 @@ class DevicePrefetcher:
             offs, total = pack_plan(src)
             i, slab = self._ring.next(total)
             base = slab.data_ptr()
+            dslab = torch.empty(total, dtype=torch.uint8, device=self.device)
+            for k, t, o in zip(packed, src, offs):
+                out[k] = dslab[o:o + t.numel() * t.element_size()].view(t.dtype).view(t.shape)
+            if patch is not None:
+                patch(out)
             for t, o in zip(src, offs):
                 n = t.numel() * t.element_size()
                 if n:
                     ctypes.memmove(base + o, t.data_ptr(), n)
-            dslab = torch.empty(total, dtype=torch.uint8, device=self.device)
             dslab.copy_(slab[:total], non_blocking=True)
             ev = torch.cuda.Event(); ev.record(self.copy_stream)
             self._ring.events[i] = ev
             self.bytes_h2d += total
-            for k, t, o in zip(packed, src, offs):
-                out[k] = dslab[o:o + t.numel() * t.element_size()].view(t.dtype).view(t.shape)
+        elif patch is not None:
+            patch(out)
         return out
 
     def _images_on_device(self, kind, dev):
@@ -284,13 +577,19 @@ class DevicePrefetcher:
         if not isinstance(batch, (list, tuple)) or len(batch) < 1:
             raise TypeError("DevicePrefetcher: the loader must yield (images, *targets) tuples")
         images, rest = batch[0], tuple(batch[1:])
+        import time
+        plan = None
+        if self.augment is not None:
+            ta = time.perf_counter()
+            items, rest, plan = self._augment(images, rest)
+            self.augment_seconds += time.perf_counter() - ta
         if self.target_transform is not None:
             rest = self.target_transform(*rest)
             if not isinstance(rest, tuple):
                 rest = (rest,)
-        import time
         t0 = time.perf_counter()
-        kind, items = classify_images(images, self.size)
+        if plan is None:
+            kind, items = classify_images(images, self.size)
         # target tensors ride in the same slab: (position in `rest`, index inside a list or None)
         where, tensors = [], []
         if self.move_targets:
@@ -301,8 +600,17 @@ class DevicePrefetcher:
                     for j, o in enumerate(obj):
                         where.append((r, j)); tensors.append(o)
         with torch.cuda.stream(self.copy_stream):
-            dev = self._h2d(list(items) + tensors)
-            img = self._images_on_device(kind, dev[:len(items)])
+            if plan is None:
+                dev = self._h2d(list(items) + tensors)
+                img = self._images_on_device(kind, dev[:len(items)])
+            else:
+                desc, arena, tmp_bytes, max_rows = plan
+                n = len(items)
+                extra = [torch.from_numpy(arena), torch.from_numpy(desc)]
+                dev = self._h2d(list(items) + tensors + extra,
+                                patch=lambda out: resolve_tile_descs(desc, [t.data_ptr() for t in out[:n]], out[-2].data_ptr()))
+                img = self.processor.run_tiles(dev[-1], desc.shape[0], max_rows, tmp_bytes, n)
+                dev = dev[:-2]
             if tensors:
                 seq = {r: type(rest[r]) for r, j in where if j is not None}       # lists / tuples of tensors keep their type
                 rest = [list(o) if r in seq else o for r, o in enumerate(rest)]
@@ -317,6 +625,28 @@ class DevicePrefetcher:
         self.batches += 1
         self.stage_seconds += time.perf_counter() - t0
         return (img,) + tuple(rest), ev
+
+    def _augment(self, images, rest):
+        """(images, labels, boxes, *more) -> the batch's uint8 sources, (labels, boxes, *more) of the AUGMENTED images, and the host half of the tile path."""
+        kind, items = classify_images(images, self.size)
+        if kind == "dense":
+            raise ValueError("DevicePrefetcher: augment= needs uint8 images: crop, flip and mosaic are folded into the uint8 resampler (one interpolation per "
+                             "source pixel), and float pixel_values have already been resized and normalised -- feed the raw pixels, or augment=None")
+        if kind == "u8_chw":
+            raise ValueError("DevicePrefetcher: augment= reads uint8 HWC images ([H,W,3] each, or [B,H,W,3]); got channels-first [B,3,S,S]")
+        if kind == "u8_hwc":
+            items = [items[0][i] for i in range(items[0].shape[0])]
+        items = [t.contiguous() for t in items]
+        if len(rest) < 2 or len(rest[0]) != len(items) or len(rest[1]) != len(items):
+            raise ValueError("DevicePrefetcher: with augment= the loader must yield (images, labels, boxes, *rest) with per-image labels and COCO xywh boxes")
+        labels = [np.asarray(torch.as_tensor(l)) for l in rest[0]]
+        boxes = [np.asarray(torch.as_tensor(b), dtype=np.float64).reshape(-1, 4) for b in rest[1]]
+        shapes = [(int(t.shape[0]), int(t.shape[1])) for t in items]
+        tiles, ob, ol = self.augment.sample(shapes, boxes, labels, self._epoch, self._index)
+        self._index += 1
+        check_tile_cover(tiles, len(items), self.size, shapes)
+        plan = build_tile_tables(shapes, tiles)
+        return items, ([torch.from_numpy(l) for l in ol], [torch.from_numpy(b) for b in ob]) + tuple(rest[2:]), plan
 
     # -- hand-over (the caller's thread and stream) ------------------------------------------------------------------------------------------------
     def _hand_over(self, staged):
@@ -369,6 +699,7 @@ class DevicePrefetcher:
 
     def __iter__(self):
         self.close()
+        self._index = 0
         it = iter(self.loader)
         if not self.threaded:
             from collections import deque
