@@ -32,7 +32,7 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler).  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's).  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
 #define OWL_ABI_VERSION 8
 const char* owl_last_error(void);
@@ -76,6 +76,18 @@ int owl_patch_embed_scratch_bytes(int64_t B, int64_t S, int64_t ps, int64_t D, i
 int owl_patch_embed_bf16(void* stream, const void* image_bf16, const void* w_pe, const float* pos, float* x_out, void* scratch, int64_t B, int64_t S, int64_t ps, int64_t D, int64_t Tp, int tile);
 /* class-token rows x[b*Tp, :] = class_embedding + pos[0, :]  (HF5:338-343)                        */
 int owl_cls_rows(void* stream, float* x, const float* cls, const float* pos, int64_t B, int64_t Tp, int64_t D);
+/* Position table at another input size than the checkpoint's (HF5:296-332 `interpolate_pos_encoding`; still ABI 8: additive).  pos f32 [g0 g0 + 1, D] is
+ * the native table (row 0 the class token, then the g0 x g0 patch rows, row-major), out f32 [g g + 1, D] the table the embeddings above are handed:
+ *   out[0] = pos[0];   out[1 + y g + x] = sum_{i, j < 4} wy_i wx_j pos[1 + cy_i g0 + cx_j]
+ * = torch.nn.functional.interpolate(mode="bicubic", align_corners=False, size=(g, g)) on the patch rows.  Per axis: source coordinate
+ * s = (o + 0.5) g0 / g - 0.5, f = floor(s), t = s - f (formed in integers: one f32 rounding); taps f - 1 .. f + 2 CLAMPED to [0, g0 - 1] (clamped taps add up
+ * on the border cell); cubic-convolution weights with A = -0.75: w0 = c2(t + 1), w1 = c1(t), w2 = c1(1 - t), w3 = c2(2 - t),
+ * c1(x) = ((A + 2) x - (A + 3)) x x + 1, c2(x) = ((A x - 5 A) x + 8 A) x - 4 A.  No antialiasing when shrinking.  g == g0 gives weights {0, 1, 0, 0}: a copy.
+ * owl_pos_resample_bwd is the exact adjoint and ACCUMULATES like every gradient entry: dpos[0] += dU[0], dpos[1 + c] += sum over the output cells whose
+ * clamped taps touch source cell c, walked in ascending (y, x) order by the one thread that owns (c, 4 columns): a gather, no atomics, bitwise reproducible.
+ * 1 <= g0, g <= 256 (g0 < 4: every tap clamped); D % 8 == 0; rows 16-byte aligned.  One launch each, no scratch.                                        */
+int owl_pos_resample(void* stream, const float* pos, float* out, int64_t g0, int64_t g, int64_t D);
+int owl_pos_resample_bwd(void* stream, const float* dU, float* dpos, int64_t g0, int64_t g, int64_t D);
 
 /* ---- LayerNorm (HF5:484-486, 721-723; eps 1e-5).  out bf16 or f32 (may alias x); stats = (mean,rstd) */
 int owl_layernorm_fwd(void* stream, const float* x, const float* gamma, const float* beta, void* out, int out_bf16, float* stats, int64_t rows, int64_t D, float eps);

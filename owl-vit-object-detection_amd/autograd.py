@@ -461,7 +461,16 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
     ops.layernorm_bwd(bw["dx"], pw["x_emb"], pw["st_pre"], P_["backbone.pre_layernorm.weight"], None, bw["dxm"] if t_emb else None,
                       G("backbone.pre_layernorm.weight") if t_pre else None, G("backbone.pre_layernorm.bias") if t_pre else None, M, D, partials=bw["part"])
     if t_emb:
-        ops.embed_bwd(bw["dxm"], G("backbone.embeddings.position_embedding.weight"), G("backbone.embeddings.class_embedding"), pw["dE"], B, T, Tp, D)
+        g_pos = G("backbone.embeddings.position_embedding.weight")
+        if model._pos_used is None:
+            ops.embed_bwd(bw["dxm"], g_pos, G("backbone.embeddings.class_embedding"), pw["dE"], B, T, Tp, D)
+        else:
+            # run grid != native grid: the batch sum lands in a zeroed [T, D] scratch (the gradient of the resampled table), and the resampler's adjoint
+            # accumulates it into the native-shape gradient; dcls and dE as ever
+            dU = pw["dU"]
+            dU.zero_()
+            ops.embed_bwd(bw["dxm"], dU, G("backbone.embeddings.class_embedding"), pw["dE"], B, T, Tp, D)
+            ops.pos_resample_bwd(dU, g_pos, cfg.native_grid, cfg.grid, D)
         ops.im2row_bf16(ws["img"], pw["patches"], B, cfg.image_size, cfg.patch_size)
         patch_weight_grad(pw["dE"], pw["patches"], G("backbone.embeddings.patch_embedding.weight").view(D, cfg.patch_k), D, cfg.patch_k, Mh,
                           scratch=dict(slab=bw["slab"], tA=bw["tAh"], tB=bw["tBh"]))

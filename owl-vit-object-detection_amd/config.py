@@ -8,6 +8,9 @@ the literal ``"layers.11"`` freeze rule (reference src/models.py:175) still sele
 L = 14 variant so frozen layers sit *above* the trainable one as in L/14.
 """
 from dataclasses import dataclass, asdict
+from math import isqrt
+
+MAX_PATCHES = 8192     # P ceiling of owl_spread_labels / owl_postprocess (one workgroup walks an image's patches)
 
 
 @dataclass(frozen=True)
@@ -22,10 +25,19 @@ class OwlConfig:
     text_dim: int        # Dt (query / class-embedding width)
     n_classes: int = 10  # C; queries = 3 * C (reference src/models.py:155-159)
     ln_eps: float = 1e-5
+    pos_grid: int = 0    # side of the NATIVE position table (the checkpoint's); 0 = `grid`.  Another value: the table is resampled to `grid` (models.OwlViT)
 
     @property
     def grid(self) -> int:
         return self.image_size // self.patch_size
+
+    @property
+    def native_grid(self) -> int:      # g0
+        return self.pos_grid or self.grid
+
+    @property
+    def pos_rows(self) -> int:         # rows of the position-embedding PARAMETER: g0 * g0 + 1, whatever the input size
+        return self.native_grid * self.native_grid + 1
 
     @property
     def patches(self) -> int:          # P
@@ -108,6 +120,35 @@ CONFIGS = {
     "tiny-l14": OwlConfig("tiny-l14", 96, 16, 128, 2, 256, 14, 64, n_classes=4),
     "small": OwlConfig("small", 192, 16, 256, 4, 512, 12, 128, n_classes=10),
 }
+
+
+def table_grid(pos_rows: int) -> int:
+    """Side g0 of a position table of `pos_rows` rows (class row + g0 x g0 patch rows); ValueError if the patch rows are no square."""
+    rows = int(pos_rows)
+    g0 = isqrt(max(rows - 1, 0))
+    if rows < 2 or g0 * g0 != rows - 1:
+        raise ValueError(f"a position table of {rows} rows is not a class row plus a square grid of patch rows; the nearest tables that are have "
+                         f"{max(g0, 1) ** 2 + 1} ({max(g0, 1)} x {max(g0, 1)}) and {(g0 + 1) ** 2 + 1} ({g0 + 1} x {g0 + 1}) rows")
+    return g0
+
+
+def check_image_size(image_size: int, patch_size: int, pos_rows: int = None) -> int:
+    """Host-side validation of a requested (square) input size: a positive multiple of the patch size, at most MAX_PATCHES patches, and -- given the
+    row count of the position table it will be run with -- a table that is a class row plus a square grid.  -> the run grid g.  Every failure is a
+    ValueError naming the nearest valid sizes."""
+    S, p = int(image_size), int(patch_size)
+    top = isqrt(MAX_PATCHES) * p
+    if S < p or S % p:
+        lo, hi = max(S // p, 1) * p, (max(S // p, 0) + 1) * p
+        near = f"{lo} and {hi}" if lo != hi and hi <= top else f"{min(lo, top)}"
+        raise ValueError(f"image_size={S} is not a positive multiple of the patch size {p}; the nearest sizes that are: {near}")
+    g = S // p
+    if g * g > MAX_PATCHES:
+        raise ValueError(f"image_size={S} gives {g * g} patches of {p} pixels; the loss and post-process kernels take at most {MAX_PATCHES} per image: "
+                         f"the largest size is {top} ({isqrt(MAX_PATCHES)} x {isqrt(MAX_PATCHES)} patches)")
+    if pos_rows is not None:
+        table_grid(pos_rows)
+    return g
 
 
 def get_config(name: str, **overrides) -> OwlConfig:

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops, weights as W
-from .config import OwlConfig, get_config
+from .config import OwlConfig, check_image_size, get_config, table_grid
 from .postprocess import PostProcess  # noqa: F401  (the reference exports it from src/models.py:122)
 
 
@@ -46,6 +46,7 @@ class _Node(nn.Module):
     """Bare container so that parameter names match the reference module tree."""
 
 
+_POS = "backbone.embeddings.position_embedding.weight"
 _LAYER_ORDER = ([f"self_attn.{p}_proj.weight" for p in "qkv"] + [f"self_attn.{p}_proj.bias" for p in "qkv"]
                 + ["self_attn.out_proj.weight", "self_attn.out_proj.bias", "layer_norm1.weight", "layer_norm1.bias", "mlp.fc1.weight", "mlp.fc1.bias",
                    "mlp.fc2.weight", "mlp.fc2.bias", "layer_norm2.weight", "layer_norm2.bias"])
@@ -82,9 +83,15 @@ class OwlViT(nn.Module):
         """trainable: None = the reference's freeze rule (weights.FREEZE_KEEP); otherwise an iterable of substrings with the reference's semantics -- a
         parameter is trainable iff any of them occurs in its name ("layers.1" therefore selects layers 1 AND 10 to 19).  The selection must be made of whole
         units (weights.BUCKET_UNITS: queries, class_predictor.dense0, box_head, backbone.post_layernorm, post_post_layernorm, each encoder layer,
-        backbone.pre_layernorm, backbone.embeddings); a partial unit or an empty selection raises ValueError."""
+        backbone.pre_layernorm, backbone.embeddings); a partial unit or an empty selection raises ValueError.
+
+        cfg.pos_grid (0 = cfg.grid): side of the NATIVE position table.  The parameter `backbone.embeddings.position_embedding.weight` keeps that
+        shape [g0 g0 + 1, D] whatever cfg.image_size is, so checkpoints, the flat bucket and optimizer states are interchangeable between input sizes; at
+        another run grid the embeddings read a resampled table (ops.pos_resample: bicubic, HF's `interpolate_pos_encoding`) the model owns."""
         super().__init__()
         self.cfg = cfg
+        if cfg.pos_grid:
+            check_image_size(cfg.image_size, cfg.patch_size, cfg.pos_rows)
         self.device_ = torch.device(device)
         if cfg.head_dim != 64:
             raise ValueError("attention kernels are built for head_dim = 64")
@@ -100,6 +107,10 @@ class OwlViT(nn.Module):
         missing = set(shapes) - set(state)
         if missing:
             raise KeyError(f"missing parameters: {sorted(missing)[:4]} ...")
+        rows = int(np.asarray(state[_POS]).shape[0])
+        if rows != cfg.pos_rows:
+            raise ValueError(f"OwlViT: the position table in `state` has {rows} rows, the config expects {cfg.pos_rows} (native grid {cfg.native_grid}); "
+                             f"build the config with pos_grid={table_grid(rows)}, or let load_model(..., image_size=) infer it")
         self._keep = None if trainable is None else tuple(trainable)
         keep = W.FREEZE_KEEP if self._keep is None else self._keep
         units, self.trainable_layers = W.trainable_units(cfg, self._keep)
@@ -180,6 +191,13 @@ class OwlViT(nn.Module):
                     if self.backward_floor != "heads":
                         self._fz[n + ".T"] = self._fz[n].t().contiguous()
         self.box_bias = box_bias_table(cfg.grid).to(self.device_)
+        # run grid != native grid: the embeddings read `_pos_used` [T, D], the native table resampled (the parameter keeps its native shape).  Frozen
+        # embeddings: made here and after every load_state_dict; trainable ones: by every forward (_forward_impl).  At the native size nothing of this exists.
+        self._pos_used = None
+        if cfg.native_grid != cfg.grid:
+            self._pos_used = torch.zeros(cfg.tokens, D, dtype=torch.float32, device=self.device_)
+            self._refresh_pos()
+            self.register_load_state_dict_post_hook(lambda module, incompatible: module._refresh_pos())
         self._ws = {}
         self._gen = 0                      # generation of the latest forward (any batch size): see _forward_impl / autograd.OwlViTFunction
         self._ws_lru = []                  # batch sizes, most recent first: workspaces of all but the newest `max_cached_batch_sizes` are dropped
@@ -359,6 +377,8 @@ class OwlViT(nn.Module):
         L = dict(x_emb=ops.zeros_rows(M, cfg.hidden, torch.float32, dev), st_pre=torch.zeros(M, 2, device=dev))
         if self._train_emb:
             L.update(patches=ops.zeros_rows(Mh, (cfg.patch_k + 7) // 8 * 8, torch.bfloat16, dev), dE=ops.zeros_rows(Mh, cfg.hidden, torch.bfloat16, dev))
+            if self._pos_used is not None:          # gradient of the resampled table [T, D], before the resampler's adjoint takes it to the native shape
+                L["dU"] = torch.zeros(cfg.tokens, cfg.hidden, dtype=torch.float32, device=dev)
         self._ws[key] = L
         return L
 
@@ -404,6 +424,17 @@ class OwlViT(nn.Module):
             dst, src = self._pe_gather
             w = self._tview("backbone.embeddings.patch_embedding.weight").view(self.cfg.hidden, self.cfg.patch_k)
             self._fz["w_pe"].index_copy_(1, dst, w.index_select(1, src))
+
+    def _refresh_pos(self):
+        """Run grid != native grid: the table the embeddings read follows the parameter (one launch; every forward with trainable embeddings calls it where
+        the parameter is known to be current, i.e. behind _wait_params)."""
+        if self._pos_used is not None:
+            cfg = self.cfg
+            ops.pos_resample(self._byname[_POS].detach(), self._pos_used, cfg.native_grid, cfg.grid, cfg.hidden)
+
+    def _pos_table(self):
+        """The position table at the run grid: the parameter itself at the native size."""
+        return self._byname[_POS] if self._pos_used is None else self._pos_used
 
     def refresh_compute_weights(self, force: bool = True):
         """bf16 copies of the trainable tensors: one cast over the flat bucket.  Every forward calls it, except the first forward after a
@@ -581,6 +612,8 @@ class OwlViT(nn.Module):
             self._wait_params()
             if from_optimizer:
                 self._refresh_patch_weight()        # (the other branch above has done it: refresh_compute_weights)
+            if self._train_emb:
+                self._refresh_pos()                 # behind the wait above: the deferred tail's AdamW has written the table this reads
 
         if image.dtype == torch.float32:
             ops.cast_bf16(image.contiguous(), ws["img"])
@@ -591,6 +624,7 @@ class OwlViT(nn.Module):
             raise TypeError("image must be float32 or bfloat16")
 
         x = ws["x"]
+        pos = self._pos_table()
         low = save and self.backward_floor in ("pre_layernorm", "embeddings")
         if low:
             # the backward goes below layer 0: keep pre_layernorm's input and row statistics (and, for the patch-embedding weight gradient, the bf16 image)
@@ -598,14 +632,14 @@ class OwlViT(nn.Module):
             if self._train_emb and img is not ws["img"]:
                 ws["img"].copy_(img)
             x_emb = pw["x_emb"]
-            ops.patch_embed(img, self._fz["w_pe"], P_["backbone.embeddings.position_embedding.weight"], x_emb, B, cfg.image_size,
+            ops.patch_embed(img, self._fz["w_pe"], pos, x_emb, B, cfg.image_size,
                             cfg.patch_size, D, Tp, scratch=self._patch_scratch(B))
-            ops.cls_rows(x_emb, P_["backbone.embeddings.class_embedding"], P_["backbone.embeddings.position_embedding.weight"], B, Tp, D)
+            ops.cls_rows(x_emb, P_["backbone.embeddings.class_embedding"], pos, B, Tp, D)
             ops.layernorm(x_emb, P_["backbone.pre_layernorm.weight"], P_["backbone.pre_layernorm.bias"], x, M, D, pw["st_pre"], cfg.ln_eps)
         else:
-            ops.patch_embed(img, self._fz["w_pe"], P_["backbone.embeddings.position_embedding.weight"], x, B, cfg.image_size,
+            ops.patch_embed(img, self._fz["w_pe"], pos, x, B, cfg.image_size,
                             cfg.patch_size, D, Tp, scratch=self._patch_scratch(B))
-            ops.cls_rows(x, P_["backbone.embeddings.class_embedding"], P_["backbone.embeddings.position_embedding.weight"], B, Tp, D)
+            ops.cls_rows(x, P_["backbone.embeddings.class_embedding"], pos, B, Tp, D)
             ops.layernorm(x, P_["backbone.pre_layernorm.weight"], P_["backbone.pre_layernorm.bias"], x, M, D, eps=cfg.ln_eps)
 
         # ---- encoder.  No kernel of it couples images, so the batch is run as `encoder_streams` sub-batches (contiguous row ranges of the
@@ -703,7 +737,7 @@ class OwlViT(nn.Module):
 
 
 def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed: int = 1234, state=None, *,
-               prompt_ids=None, text_state=None, vocab=None, merges=None, trainable=None):
+               prompt_ids=None, text_state=None, vocab=None, merges=None, trainable=None, image_size=None):
     """ref src/models.py:149-191.  The reference downloads `google/owlvit-base-patch32` and runs the
     CLIP text tower once to initialise the query bank; neither box has network access, so weights
     come from `state` (name -> array, reference parameter names) or, by default, the deterministic
@@ -721,9 +755,19 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
     tokenizer.ClipBPE, id for id `transformers.CLIPTokenizer`), i.e. the unchanged `load_model(labelmap, device)` call of ref main.py:42 plus the two
     paths gives the reference's query bank.
 
-    `trainable` (None = the reference's freeze rule): the substring list of that rule, as a user of the reference would edit it -- see OwlViT."""
+    `trainable` (None = the reference's freeze rule): the substring list of that rule, as a user of the reference would edit it -- see OwlViT.
+
+    `image_size` (None = the architecture's): the square input size the model is built for, a multiple of the patch size with at most 8192 patches
+    (HF's `interpolate_pos_encoding=True`, HF5:296-332).  The native grid of the position table is read off `state`'s table (a checkpoint's, through
+    weights.from_hf_state_dict) or is the architecture's; the parameter keeps that shape and the embeddings read a bicubic resample of it, so
+    state dicts and FusedAdamW states move freely between sizes.  At the native size nothing changes."""
     n_classes = len(labelmap)
     cfg = get_config(arch, n_classes=n_classes)
+    g0 = table_grid(np.asarray(state[_POS]).shape[0]) if (state is not None and _POS in state) else cfg.grid
+    if image_size is not None or g0 != cfg.grid:
+        S = cfg.image_size if image_size is None else int(image_size)
+        g = check_image_size(S, cfg.patch_size, g0 * g0 + 1)
+        cfg = cfg.replace(image_size=S, pos_grid=0 if g0 == g else g0)
     if (vocab is None) != (merges is None):
         raise ValueError("load_model: vocab= and merges= go together (the CLIP vocab.json and merges.txt)")
     if vocab is not None:

@@ -283,6 +283,24 @@ def embed_bwd(dx, dpos, dcls, dE, B, T, Tp, D):
     _lib.call("owl_embed_bwd", stream(), dx, dpos, dcls, dE, B, T, Tp, D)
 
 
+def pos_resample(pos, out, g0, g, D):
+    """out [g g + 1, D] = the native position table pos [g0 g0 + 1, D] at grid g: class row copied, patch rows bicubic (align_corners=False, A = -0.75, clamped
+    taps -- include/owl_hip.h)."""
+    _chk(pos, torch.float32, "pos"); _chk(out, torch.float32, "out")
+    if pos.numel() < (g0 * g0 + 1) * D or out.numel() < (g * g + 1) * D:
+        raise ValueError("pos_resample: pos must hold [g0 g0 + 1, D], out [g g + 1, D]")
+    _lib.call("owl_pos_resample", stream(), pos, out, g0, g, D)
+    return out
+
+
+def pos_resample_bwd(dU, dpos, g0, g, D):
+    """The adjoint of pos_resample: dpos [g0 g0 + 1, D] += K^T dU [g g + 1, D] (a gather over source cells: no atomics, bitwise reproducible)."""
+    _chk(dU, torch.float32, "dU"); _chk(dpos, torch.float32, "dpos")
+    if dU.numel() < (g * g + 1) * D or dpos.numel() < (g0 * g0 + 1) * D:
+        raise ValueError("pos_resample_bwd: dU must hold [g g + 1, D], dpos [g0 g0 + 1, D]")
+    _lib.call("owl_pos_resample_bwd", stream(), dU, dpos, g0, g, D)
+
+
 def im2row_bf16(image, out, B, S, ps):
     """out [>= B (S / ps)^2, ld] bf16 <- patches of image [B, 3, S, S] bf16, columns in the conv weight's (c, i, j) order; columns past 3 ps^2 are left alone."""
     _chk(image, torch.bfloat16, "image"); _chk(out, torch.bfloat16, "out")

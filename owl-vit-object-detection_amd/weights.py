@@ -93,7 +93,7 @@ def param_shapes(cfg: OwlConfig) -> "OrderedDict[str, tuple]":
     s["queries"] = (1, cfg.queries, Dt)
     s["backbone.embeddings.class_embedding"] = (D,)
     s["backbone.embeddings.patch_embedding.weight"] = (D, 3, p, p)
-    s["backbone.embeddings.position_embedding.weight"] = (cfg.tokens, D)
+    s["backbone.embeddings.position_embedding.weight"] = (cfg.pos_rows, D)          # the NATIVE table (= cfg.tokens rows unless cfg.pos_grid is set)
     s["backbone.pre_layernorm.weight"] = (D,)
     s["backbone.pre_layernorm.bias"] = (D,)
     for i in range(cfg.layers):
@@ -210,7 +210,7 @@ TRAINED_LIKE_PROFILES = {
 
 def trained_like(cfg: OwlConfig, base: "OrderedDict[str, np.ndarray]", seed: int = 1234, profile: str = "trained_like") -> "OrderedDict[str, np.ndarray]":
     t = TRAINED_LIKE_PROFILES[profile]
-    D, P = cfg.hidden, cfg.patches
+    D, P = cfg.hidden, cfg.pos_rows - 1          # (the sink tokens are rows of the native position table)
     out = OrderedDict((k, v.copy()) for k, v in base.items())
     ch = [int(f * D) for f in t["massive_channels"]]
     cs = int(t["sink_channel"] * D)
