@@ -10,14 +10,16 @@ Parameter gradients are ACCUMULATED by the kernels directly into `model.flat_gra
 .grad is a view of that bucket), so `loss.backward()` leaves one contiguous buffer ready for the single
 all-reduce + optimizer step; the Function therefore returns no per-parameter tensors.
 """
+from collections import namedtuple
+
 import torch
 
 from . import _lib, ops
 
 
 DW_ITEMS = 256             # (tile, split) work items a weight-gradient GEMM is cut into: one per CU (bench.py --dw-items: fewer = less slab traffic and CUs left to the dX chain; measured, profiles/r06_tail.md)
-TN_SMALL_N = True          # round 6: dW products with fewer than 256 output rows (the 32 x Dt prompt gradient) on the TN kernel too; False = explicit transposes + NT split-K (A/B)
-FOLD_BIAS_COLSUM = True    # round 6: bias gradients of the TN-kernel Linears come out of the dW GEMM's own pass (csrc/gemm_tn.hip); False = the separate colsum_bf16 pass (A/B: bench.py --fold-bias 0)
+TN_SMALL_N = True          # weight-gradient products with at most 64 output rows (the 32 x Dt prompt gradient) on the TN kernel too; False = explicit transposes + NT split-K (A/B)
+FOLD_BIAS_COLSUM = True    # bias gradients of the TN-kernel Linears come out of the dW GEMM's own pass (csrc/gemm_tn.hip); False = the separate colsum_bf16 pass (A/B: bench.py --fold-bias 0)
 
 
 def _grads_attached(model) -> bool:
@@ -96,16 +98,13 @@ def _bws(model, B):
     Mp, Mhp = ops.pad_rows(M), ops.pad_rows(Mh)
     bf, f32 = torch.bfloat16, torch.float32
     z = ops.zeros_rows
-    wide = max(3 * D, I)
-    tn_all = all(v % 256 == 0 for v in (D, I, Dt))          # every token-row dW goes through the TN kernel (gemm_tn.hip)
     Qg = _routed_cols(model)                                 # columns of the routed upstream G = rows of dqhat: 32, or the wide head's Qp
-    Kpe = cfg.patch_k if model._train_emb else 0             # trainable embeddings: the patch-embedding weight gradient [D, 3 p p] shares the head-row scratch
-    pe_nt = Kpe and not (Kpe % 256 == 0 and D % 256 == 0)    # ... on the transposes + NT split-K route
+    sz = _dw_sizes(cfg, Qg, model._train_emb)
     ws = dict(
         de=z(Mh, Dt, bf, dev), dqhat=torch.zeros(Qg, Dt, device=dev), du1=z(Mh, D, bf, dev), du0=z(Mh, D, bf, dev),
         g32=z(Mh, Qg, bf, dev), e_bf=z(Mh, Dt, bf, dev),
         box_part=torch.zeros(_lib.load().owl_box_final_bwd_blocks(Mh), 5 * D + 4, device=dev),
-        slab=torch.zeros(max(_slab_elems(cfg, Qg), _dw_slab_elems(D, (Kpe + 7) // 8 * 8) if Kpe else 0), device=dev),
+        slab=torch.zeros(sz.slab, device=dev),
         sink=torch.zeros(4 * D + 8, device=dev),          # where kernels that must run leave the gradients of FROZEN tensors (never read; not in the bucket)
         # per-split partial sums of the bias gradients (one row of n_out floats per split of the dW GEMM; at most 256 splits); the class head's chain has its own
         bslab=torch.zeros(256 * max(3 * D, I, Dt), device=dev), bslab2=torch.zeros(256 * max(D, Dt), device=dev),
@@ -120,18 +119,23 @@ def _bws(model, B):
         dxb2=z(M, D, bf, dev),                                              # second bf16 dx of the trainable layer (the first one is still being read)
         # transposed-operand scratch for the dW GEMMs; token-row and head-row users get their own buffers so
         # that the zero pad columns [rows, rows_pad) of each are never dirtied by the other row count
-        # (only the shapes the TN kernel does not take need them: feature counts that are not multiples of 256 -- the
-        # parity-test configs -- and the 32 x Dt prompt-gradient product)
-        tA=None if tn_all else torch.zeros(wide, Mp, dtype=bf, device=dev),
-        tB=None if tn_all else torch.zeros(wide, Mp, dtype=bf, device=dev),
-        tAh=torch.zeros(max(32 if tn_all else max(D, Dt, Qg if model.wide_head else 0), D if pe_nt else 0), Mhp, dtype=bf, device=dev),
-        tBh=torch.zeros(max(D, Dt, Kpe if pe_nt else 0), Mhp, dtype=bf, device=dev),
-        wT=torch.zeros(wide * max(D, I), dtype=bf, device=dev),
+        # (only the products _dw_plan() sends down the NT route need them: the parity-test configs' and the 32 x Dt prompt-gradient product; the
+        #  patch-embedding weight gradient, where embeddings train, shares the head-row pair)
+        tA=torch.zeros(sz.tok_rows, Mp, dtype=bf, device=dev) if sz.tok_rows else None,
+        tB=torch.zeros(sz.tok_rows, Mp, dtype=bf, device=dev) if sz.tok_rows else None,
+        tAh=torch.zeros(sz.tAh_rows, Mhp, dtype=bf, device=dev),
+        tBh=torch.zeros(sz.tBh_rows, Mhp, dtype=bf, device=dev),
+        wT=torch.zeros(max(3 * D, I) * max(D, I), dtype=bf, device=dev),
         # the class head's backward runs beside the box head's on the side stream: its own split-K slab and transposed-weight scratch
-        slab2=torch.zeros(max(_split_k(Dt, D, 1 << 30) * Dt * D, _dw_slab_elems(Qg, Dt)), device=dev),
+        slab2=torch.zeros(sz.slab2, device=dev),
         wT2=torch.zeros(Dt * D, dtype=bf, device=dev),
-        tn_all=tn_all,
+        tn_all=sz.tn_all,
     )
+    # the scratch of one weight-gradient launch (weight_grad), by who launches it -- the same buffers, no memory of their own:
+    # this stream at head rows (the heads, the patch embedding); the class head where it runs on the side stream; the encoder layers' weight-gradient stream
+    ws["dw_main"] = dict(slab=ws["slab"], part=ws["part"], bslab=ws["bslab"], tA=ws["tAh"], tB=ws["tBh"], tn_all=sz.tn_all)
+    ws["dw_class"] = dict(slab=ws["slab2"], part=ws["part2"], bslab=ws["bslab2"], tA=ws["tAh"], tB=ws["tBh"], tn_all=sz.tn_all)
+    ws["dw_enc"] = dict(slab=ws["slab"], part=ws["part2"], bslab=ws["bslab"], tA=ws["tA"], tB=ws["tB"], tn_all=sz.tn_all)
     model._ws[key] = ws
     return ws
 
@@ -144,65 +148,104 @@ def _split_k(n_rows_out, n_cols_out, k):
     return max(1, min(k // 64, slots // tiles))
 
 
+def _qkv_grads(model, i):
+    """f32 [3D, D] and [3D] views of the bucket: the gradients of trainable layer i's fused q / k / v weight (models.OwlViT._wqkv) and bias."""
+    D, pre = model.cfg.hidden, f"backbone.encoder.layers.{i}.self_attn.q_proj."
+    o, ob = model.flat_offsets[pre + "weight"], model.flat_offsets[pre + "bias"]
+    return model.flat_grad[o: o + 3 * D * D].view(3 * D, D), model.flat_grad[ob: ob + 3 * D]
+
+
 def _routed_cols(model):
     """Columns of the class head's routed upstream G (= rows of dqhat): one 32-column tile, or the wide head's Qp (a multiple of 256)."""
     return ops.wide_qp(model.cfg.n_classes) if model.wide_head else 32
 
 
-def _dw_slab_elems(n_out, n_in):
-    """f32 elements of the split-K slabs of one dW shape on either route of backward_impl's dW(): the NT kernel's _split_k() splits, or -- a shape
-    the TN kernel takes whole (both sides multiples of 256) -- its DW_ITEMS // tiles splits, which is more for fewer than 512 output rows."""
-    splits = _split_k(n_out, n_in, 1 << 30)
-    if n_out % 256 == 0 and n_in % 256 == 0:
-        splits = max(splits, 256 // ((n_out // 256) * (n_in // 256)))
-    return splits * n_out * n_in
+DwPlan = namedtuple("DwPlan", "tn splits n_in_pad slab_elems")
+DwSizes = namedtuple("DwSizes", "tn_all slab slab2 tok_rows tAh_rows tBh_rows")
 
 
-def _slab_elems(cfg, routed_cols=32):
-    """f32 elements of the split-K slab scratch: max over the dW shapes of splits * n_out * n_in."""
+def _dw_plan(n_out, n_in, *, bias=False, tn_all=False, rows=None):
+    """How one weight-gradient product grad_w[n_out, n_in] (+)= dy[rows, n_out]^T x[rows, n_in] is launched (weight_grad) -- the one place that decides it.
+    tn: the TN kernel (csrc/gemm_tn.hip) reads dy / x where they lie.  It takes the products whose two sides are multiples of 256, and -- TN_SMALL_N -- one
+      with at most 64 output rows (a multiple of 8: one 256-wide n tile of which those rows are kept; the 32 x Dt prompt gradient, 92 us -> ~30,
+      profiles/r06_tail.md) where every token-row product is on the kernel too (`tn_all`) and no bias gradient rides along (`bias`).  Every other product:
+      two explicit transposes, then the NT split-K GEMM over n_in padded to a multiple of 8 (`n_in_pad`; L/14's 588 patch columns run as 592).
+    splits: the split count to request -- DW_ITEMS (at most 256, one per CU) work items over the TN kernel's 256 x 256 tiles, or _split_k() of the NT
+      kernel's own tiles at `rows` (None: at any row count).  The kernels may use fewer, never more.
+    slab_elems: f32 elements the split-K slabs of that route can take at any row count and any DW_ITEMS (the scratch outlives a change of the switch)."""
+    if n_in % 256 == 0 and (n_out % 256 == 0 or (TN_SMALL_N and n_out % 8 == 0 and n_out <= 64 and tn_all and not bias)):
+        tiles = ((n_out + 255) // 256) * (n_in // 256)
+        return DwPlan(True, max(1, min(DW_ITEMS, 256) // tiles), n_in, max(1, 256 // tiles) * n_out * n_in)
+    n_in_pad = (n_in + 7) // 8 * 8
+    most = _split_k(n_out, n_in_pad, 1 << 30)
+    return DwPlan(False, most if rows is None else _split_k(n_out, n_in_pad, ops.pad_rows(rows)), n_in_pad, most * n_out * n_in_pad)
+
+
+def _dw_sizes(cfg, routed_cols=32, train_emb=False):
+    """Scratch of backward_impl's weight-gradient launches, from _dw_plan() of every product it can launch (no device, no tensor) -> tn_all: every product of
+    the encoder's and the class head's widths is on the TN kernel; f32 elements of the split-K slab and of the class-head lane's own; rows of the token-row
+    transposed-operand pair tA / tB (0: none) and of the head-row pair (tAh holds dy^T: n_out rows, tBh holds x^T: n_in rows)."""
     D, I, Dt = cfg.hidden, cfg.mlp, cfg.text_dim
-    shapes = [(3 * D, D), (D, D), (I, D), (D, I), (Dt, D)]
-    return max(max(_split_k(a, b, 1 << 30) * a * b for a, b in shapes), _dw_slab_elems(routed_cols, Dt))
+    plan = lambda n_out, n_in, tn_all=False: (n_out, n_in, _dw_plan(n_out, n_in, tn_all=tn_all))          # (a bias gradient bears on the small-n_out exception alone: the routed product, which has none)
+    enc = [plan(3 * D, D), plan(D, D), plan(I, D), plan(D, I)]          # token rows
+    tn_all = all(p.tn for _, _, p in enc + [plan(Dt, D)])
+    # head rows: the class head's products, which run on either lane (the routed one with and without the small-n_out exception: TN_SMALL_N may flip after
+    # the workspaces exist), the box head's and the patch embedding's
+    cls = [plan(Dt, D), plan(routed_cols, Dt, tn_all), plan(routed_cols, Dt)]
+    head = cls + [plan(D, D)] + ([plan(D, cfg.patch_k)] if train_emb else [])
+    nt = [(n_out, n_in) for n_out, n_in, p in head if not p.tn]
+    # (floors: the head widths, or one 32-row tile where every token-row product is on the TN kernel; what the NT products need only ever raises them)
+    return DwSizes(tn_all, slab=max(p.slab_elems for _, _, p in enc + head), slab2=max(p.slab_elems for _, _, p in cls),
+                   tok_rows=0 if tn_all else max(max(n_out, n_in) for n_out, n_in, _ in enc),
+                   tAh_rows=max([32 if tn_all else max(D, Dt)] + [n_out for n_out, _ in nt]), tBh_rows=max([D, Dt] + [n_in for _, n_in in nt]))
+
+
+def weight_grad(dy, x, grad_w, n_out, n_in, rows, scratch, grad_b=None, accumulate=1):
+    """grad_w[n_out, n_in] (+)= dy[rows, n_out]^T x[rows, n_in];  grad_b += colsum(dy), on the route _dw_plan() picks: split-K GEMM into f32 slabs ->
+    deterministic slab reduction.  dy [>= rows, n_out] and x [>= rows, ld >= n_in] bf16.
+    scratch: dict(slab; with a bias gradient also part, bslab; for the NT route tA [>= n_out, pad_rows(rows)], tB [>= n_in, pad_rows(rows)]; tn_all) --
+    one of _bws()'s three.  Pad columns [rows, pad_rows(rows)) of tA / tB stay zero: never written, buffers start zeroed."""
+    plan = _dw_plan(n_out, n_in, bias=grad_b is not None, tn_all=scratch.get("tn_all", False), rows=rows)
+    slab = scratch["slab"]
+    if plan.tn:
+        # no token-major copies (LDS transpose-reads).  The bias gradient (column sums of dy) comes out of the same pass as per-split partial sums and is
+        # added up like the weight slabs
+        bs = scratch["bslab"] if (grad_b is not None and FOLD_BIAS_COLSUM) else None
+        if grad_b is not None and bs is None:          # (A/B switch off: the column-sum kernel)
+            ops.colsum_bf16(dy, grad_b, rows, n_out, partials=scratch["part"])
+        ns = ops.gemm_tn_slab(dy, x, slab, rows, n_out, n_in, plan.splits, bias_slab=bs)
+        _lib.call("owl_slab_reduce", ops.stream(), slab, grad_w, n_out * n_in, n_out * n_in, ns, accumulate)
+        if bs is not None:
+            _lib.call("owl_slab_reduce", ops.stream(), bs, grad_b, n_out, n_out, ns, 1)
+        return
+    tA, tB = scratch["tA"], scratch["tB"]
+    ld, Kp = ops.pad_rows(rows), plan.n_in_pad
+    assert tA.shape[1] == ld and tB.shape[1] == ld and tA.shape[0] >= n_out and tB.shape[0] >= n_in
+    ops.transpose_colsum(dy, tA, grad_b, rows, n_out, ld_in=dy.shape[-1], ld_out=ld, partials=scratch.get("part"))
+    ops.transpose_colsum(x, tB, None, rows, n_in, ld_in=x.shape[-1], ld_out=ld)
+    ns = _lib.load().owl_gemm_effective_splits(ld, plan.splits)
+    # (rows [n_in, Kp) of the W operand do not exist: w_rows clamps the loads, and the row-by-row reducer leaves those columns of the slabs alone)
+    ops.gemm(ops.EPI_SLAB_F32, tA, tB, slab, M=n_out, N=Kp, K=ld, lda=ld, ldw=ld, ldo=Kp, a_rows=n_out, w_rows=n_in, splits=plan.splits)
+    if Kp == n_in:
+        _lib.call("owl_slab_reduce", ops.stream(), slab, grad_w, n_out * n_in, n_out * n_in, ns, accumulate)
+    else:
+        _lib.call("owl_slab_reduce_rows", ops.stream(), slab, grad_w, n_out, n_in, Kp, n_out * Kp, ns, accumulate)
 
 
 def patch_weight_grad(dE, patches, grad_w, D, K, rows, scratch=None, accumulate=1):
-    """grad_w [D, K] (+)= dE[rows, D]^T patches[rows, K] -- the patch-embedding weight gradient, on the routes of backward_impl's dW(): the TN kernel where
-    both sides are multiples of 256, transposes + NT split-K otherwise (K no multiple of 8, L/14's 588: the product runs 8-padded and the slabs are reduced
-    row by row).  dE [>= rows, D] and patches [>= rows, ld >= K] bf16; scratch: dict(slab, tA [>= D, pad_rows(rows)], tB [>= K, pad_rows(rows)]) with the pad
-    columns [rows, pad_rows(rows)) of tA / tB zero (default: allocated here)."""
-    rows_pad = ops.pad_rows(rows)
-    Kp = (K + 7) // 8 * 8
-    tn = K % 256 == 0 and D % 256 == 0
+    """grad_w [D, K] (+)= dE[rows, D]^T patches[rows, K] -- the patch-embedding weight gradient: weight_grad() without a bias (scratch as there; default:
+    allocated here)."""
     if scratch is None:
-        dev = dE.device
-        scratch = dict(slab=torch.zeros(_dw_slab_elems(D, Kp), device=dev),
-                       tA=None if tn else torch.zeros(D, rows_pad, dtype=torch.bfloat16, device=dev), tB=None if tn else torch.zeros(K, rows_pad, dtype=torch.bfloat16, device=dev))
-    slab = scratch["slab"]
-    if tn:
-        tiles = (D // 256) * (K // 256)
-        ns = ops.gemm_tn_slab(dE, patches, slab, rows, D, K, max(1, min(DW_ITEMS, 256) // tiles))
-        _lib.call("owl_slab_reduce", ops.stream(), slab, grad_w, D * K, D * K, ns, accumulate)
-        return
-    tA, tB = scratch["tA"], scratch["tB"]
-    ld = tA.shape[1]
-    assert ld == rows_pad and tB.shape[1] == rows_pad and tA.shape[0] >= D and tB.shape[0] >= K
-    ops.transpose_colsum(dE, tA, None, rows, D, ld_in=dE.shape[-1], ld_out=ld)
-    ops.transpose_colsum(patches, tB, None, rows, K, ld_in=patches.shape[-1], ld_out=ld)
-    want = _split_k(D, Kp, rows_pad)
-    ns = _lib.load().owl_gemm_effective_splits(rows_pad, want)
-    # (rows [K, Kp) of the W operand do not exist: w_rows clamps the loads, and the reducer below leaves those columns of the slabs alone)
-    ops.gemm(ops.EPI_SLAB_F32, tA, tB, slab, M=D, N=Kp, K=rows_pad, lda=ld, ldw=ld, ldo=Kp, a_rows=D, w_rows=K, splits=want)
-    if Kp == K:
-        _lib.call("owl_slab_reduce", ops.stream(), slab, grad_w, D * K, D * K, ns, accumulate)
-    else:
-        _lib.call("owl_slab_reduce_rows", ops.stream(), slab, grad_w, D, K, Kp, D * Kp, ns, accumulate)
+        plan, ld, dev = _dw_plan(D, K), ops.pad_rows(rows), dE.device
+        scratch = dict(slab=torch.zeros(plan.slab_elems, device=dev),
+                       tA=None if plan.tn else torch.zeros(D, ld, dtype=torch.bfloat16, device=dev), tB=None if plan.tn else torch.zeros(K, ld, dtype=torch.bfloat16, device=dev))
+    weight_grad(dE, patches, grad_w, D, K, rows, scratch, accumulate=accumulate)
 
 
 def backward_impl(model, B, d_boxes, d_sims, sims):
     cfg = model.cfg
     D, I, H, Tp, T, P, Dt, C = cfg.hidden, cfg.mlp, cfg.heads, cfg.tokens_padded, cfg.tokens, cfg.patches, cfg.text_dim, cfg.n_classes
     M, Mh = B * Tp, B * P
-    Mp, Mhp = ops.pad_rows(M), ops.pad_rows(Mh)
     ws, bw = model._workspace(B), _bws(model, B)
     P_ = model._byname
     model._wait_params()
@@ -223,45 +266,16 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
     if pre_wt is not None:
         torch.cuda.current_stream().wait_event(model._wt_event)
 
-    def wT(name, rows, cols, buf="wT"):
+    def wT(name, rows, cols, buf=bw["wT"]):
         """bf16 transpose of a weight [rows, cols] -> [cols, rows].  Trainable: the forward's pre-transposed copy, or (pretranspose off) made here in scratch;
         frozen but crossed by the dX chain: the static copy made at construction."""
         if name not in model.flat_offsets:
             return model._fz[name + ".T"]
         if pre_wt is not None:
             return pre_wt[name]
-        out = bw[buf][: rows * cols].view(cols, rows)
+        out = buf[: rows * cols].view(cols, rows)
         ops.transpose_bf16(tv(name), out, rows, cols)
         return out
-
-    def dW(dy, x, grad_w, n_out, n_in, rows, rows_pad, grad_b=None, accumulate=1, part="part", slab="slab"):
-        """grad_w[n_out, n_in] (+)= dy[rows, n_out]^T x[rows, n_in];  grad_b += colsum(dy).
-        Token-major operand copies (transposes) -> split-K GEMM into f32 slabs -> deterministic slab reduction.
-        Pad columns [rows, rows_pad) of the scratch stay zero: never written, buffers start zeroed."""
-        # (round 6: also the class head's 32 x Dt prompt-gradient product -- one 256-wide n tile of which 32 rows are kept; it used to go through two explicit
-        #  transposes + the NT split-K kernel: 92 us against ~30, bench.py --tn-small-n 0 / 1, profiles/r06_tail.md)
-        if n_in % 256 == 0 and (n_out % 256 == 0 or (TN_SMALL_N and n_out % 8 == 0 and n_out <= 64 and bw["tn_all"] and grad_b is None)):
-            # TN kernel: reads dy / x where they lie (LDS transpose-reads), no token-major copies.  The bias gradient (column sums of dy) comes out of the
-            # same pass as per-split partial sums (round 6: it was a second read of dy by a kernel of its own) and is added up like the weight slabs
-            tiles = ((n_out + 255) // 256) * (n_in // 256)
-            bs = bw["bslab2" if slab == "slab2" else "bslab"] if (grad_b is not None and FOLD_BIAS_COLSUM) else None
-            if grad_b is not None and bs is None:          # (A/B switch off: the column-sum kernel of rounds 2-5)
-                ops.colsum_bf16(dy, grad_b, rows, n_out, partials=bw[part])
-            ns = ops.gemm_tn_slab(dy, x, bw[slab], rows, n_out, n_in, max(1, min(DW_ITEMS, 256) // tiles), bias_slab=bs)          # (the slab scratch is sized for 256 items)
-            _lib.call("owl_slab_reduce", ops.stream(), bw[slab], grad_w, n_out * n_in, n_out * n_in, ns, accumulate)
-            if bs is not None:
-                _lib.call("owl_slab_reduce", ops.stream(), bs, grad_b, n_out, n_out, ns, 1)
-            return
-        tA, tB = (bw["tAh"], bw["tBh"]) if rows == Mh else (bw["tA"], bw["tB"])
-        ld = tA.shape[1]
-        assert ld == rows_pad
-        ops.transpose_colsum(dy, tA, grad_b, rows, n_out, ld_in=dy.shape[-1], ld_out=ld, partials=bw[part])
-        ops.transpose_colsum(x, tB, None, rows, n_in, ld_in=x.shape[-1], ld_out=ld)
-        want = _split_k(n_out, n_in, rows_pad)
-        ns = _lib.load().owl_gemm_effective_splits(rows_pad, want)
-        ops.gemm(ops.EPI_SLAB_F32, tA, tB, bw[slab], M=n_out, N=n_in, K=rows_pad, lda=ld, ldw=ld, ldo=n_in,
-                 a_rows=n_out, w_rows=n_in, splits=want)
-        _lib.call("owl_slab_reduce", ops.stream(), bw[slab], grad_w, n_out * n_in, n_out * n_in, ns, accumulate)
 
     # The two heads only meet in d(feats): with sub-batch streams on (and every dW on the TN kernel, so that the heads share no transposed-operand
     # scratch) the class head's backward runs on the side stream with its own slab / reduction / transposed-weight scratch, beside the box
@@ -278,7 +292,7 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
     if hs is not main0:
         ev_h[0].record(main0)
         hs.wait_event(ev_h[0])
-    cs, cp, cw = ("slab2", "part2", "wT2") if hs is not main0 else ("slab", "part", "wT")
+    cdw, cw = (bw["dw_class"], bw["wT2"]) if hs is not main0 else (bw["dw_main"], bw["wT"])
     # ---- class head ---------------------------------------------------------------------------------
     with torch.cuda.stream(hs):
         if t_q or t_cls or below_heads:
@@ -286,15 +300,15 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
                 Qp = bw["g32"].shape[1]
                 ops.class_sims_wide_bwd(d_sims, sims, ws["argmax"], ws["inv_norm"], ws["e"], ws["qhat"], bw["de"], bw["g32"], bw["e_bf"], Mh, Dt, C)
                 if t_q:
-                    dW(bw["g32"], bw["e_bf"], bw["dqhat"], Qp, Dt, Mh, Mhp, None, accumulate=0, part=cp, slab=cs)          # dqhat = G^T e
+                    weight_grad(bw["g32"], bw["e_bf"], bw["dqhat"], Qp, Dt, Mh, cdw, accumulate=0)          # dqhat = G^T e
                     ops.query_normalize_wide_bwd(bw["dqhat"], P_["queries"], G("queries"), cfg.queries, Dt)
             else:
                 ops.class_sims_bwd(d_sims, sims, ws["argmax"], ws["inv_norm"], ws["e"], ws["qhat"], bw["de"], bw["g32"], bw["e_bf"], Mh, Dt, C)
                 if t_q:
-                    dW(bw["g32"], bw["e_bf"], bw["dqhat"], 32, Dt, Mh, Mhp, None, accumulate=0, part=cp, slab=cs)          # dqhat = G^T e
+                    weight_grad(bw["g32"], bw["e_bf"], bw["dqhat"], 32, Dt, Mh, cdw, accumulate=0)          # dqhat = G^T e
                     _lib.call("owl_query_normalize_bwd", ops.stream(), bw["dqhat"], P_["queries"], G("queries"), cfg.queries, Dt)
             if t_cls:
-                dW(bw["de"], ws["feats"], G("class_predictor.dense0.weight"), Dt, D, Mh, Mhp, G("class_predictor.dense0.bias"), part=cp, slab=cs)
+                weight_grad(bw["de"], ws["feats"], G("class_predictor.dense0.weight"), Dt, D, Mh, cdw, G("class_predictor.dense0.bias"))
             if below_heads:
                 ops.gemm(ops.EPI_F32, bw["de"], wT("class_predictor.dense0.weight", Dt, D, buf=cw), bw["dfeats"], M=Mh, N=D, K=Dt)
         if hs is not main0:
@@ -310,10 +324,10 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
         ops.box_final_bwd(d_boxes, ws["sig"], ws["hb1"], ws["ub1"], P_["box_head.dense2.weight"], bw["du1"], bw["box_part"], gw2, Mh, D,
                           du1_colsum=G("box_head.dense1.bias") if t_box else None)          # (dense1's bias gradient from the same pass: no column-sum launch over du1)
         if t_box:
-            dW(bw["du1"], ws["hb0"], G("box_head.dense1.weight"), D, D, Mh, Mhp, None)
+            weight_grad(bw["du1"], ws["hb0"], G("box_head.dense1.weight"), D, D, Mh, bw["dw_main"])
         ops.gemm(ops.EPI_DGELU_BF16, bw["du1"], wT("box_head.dense1.weight", D, D), bw["du0"], aux=ws["ub0"], M=Mh, N=D, K=D)
         if t_box:
-            dW(bw["du0"], ws["feats"], G("box_head.dense0.weight"), D, D, Mh, Mhp, G("box_head.dense0.bias"))
+            weight_grad(bw["du0"], ws["feats"], G("box_head.dense0.weight"), D, D, Mh, bw["dw_main"], G("box_head.dense0.bias"))
         if below_heads:
             w0T = wT("box_head.dense0.weight", D, D)
     if hs is not main0:
@@ -381,7 +395,7 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
         # idle, and vice versa.  Same kernels on the same operands: same bits.  The side stream owns the split-K slab from here on and has its
         # own reduction scratch; the second bf16 dx goes to its own buffer because dW(fc2) may still be reading the first.  The side stream is
         # in-order: the dW chains of successive trainable layers queue behind each other on the one set of scratch.
-        tl, Lt = LP(i), model._layer_ws(B, i)
+        tl, Lt, dwe = LP(i), model._layer_ws(B, i), bw["dw_enc"]
         main = torch.cuda.current_stream()
         side = S(1) if model.encoder_streams > 1 else main
         evs = model._dw_events
@@ -398,31 +412,27 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
         # MLP
         if not fc2_bias_done:     # (the last layer's fc2 bias gradient came out of merge_ln_bwd, that of a layer below a trainable one out of its LayerNorm 1 backward)
             ops.colsum_f32(bw["dx"], G(tl + "mlp.fc2.bias"), M, D, partials=bw["part"])
-        on_side(0, lambda: dW(bw["dxb"], Lt["g"], G(tl + "mlp.fc2.weight"), D, I, M, Mp, part="part2"))
+        on_side(0, lambda: weight_grad(bw["dxb"], Lt["g"], G(tl + "mlp.fc2.weight"), D, I, M, dwe))
         dxc = 1 if side is main else 2          # (the weight-gradient GEMMs run beside the dX chain: ops.gemm's small-problem rule counts them)
         ops.gemm(ops.EPI_DQGELU_BF16, bw["dxb"], wT(tl + "mlp.fc2.weight", D, I), bw["du"], aux=Lt["gp"], M=M, N=I, K=D, concurrency=dxc)
-        on_side(1, lambda: dW(bw["du"], Lt["h2"], G(tl + "mlp.fc1.weight"), I, D, M, Mp, G(tl + "mlp.fc1.bias"), part="part2"))
+        on_side(1, lambda: weight_grad(bw["du"], Lt["h2"], G(tl + "mlp.fc1.weight"), I, D, M, dwe, G(tl + "mlp.fc1.bias")))
         ops.gemm(ops.EPI_BIAS_BF16, bw["du"], wT(tl + "mlp.fc1.weight", I, D), bw["dh"], M=M, N=D, K=I, concurrency=dxc)
         ops.layernorm_bwd(bw["dh"], Lt["x_mid"], Lt["st2"], P_[tl + "layer_norm2.weight"], bw["dx"], bw["dxm"],
                           G(tl + "layer_norm2.weight"), G(tl + "layer_norm2.bias"), M, D, dx_bf16=bw["dxb2"], partials=bw["part"],
                           dx_colsum=G(tl + "self_attn.out_proj.bias"))     # (dx here = d(x + out-proj output): its column sums are that bias's gradient)
         # attention
-        on_side(2, lambda: dW(bw["dxb2"], Lt["att"], G(tl + "self_attn.out_proj.weight"), D, D, M, Mp, part="part2"))
+        on_side(2, lambda: weight_grad(bw["dxb2"], Lt["att"], G(tl + "self_attn.out_proj.weight"), D, D, M, dwe))
         woT = wT(tl + "self_attn.out_proj.weight", D, D)
         ops.gemm(ops.EPI_BIAS_BF16, bw["dxb2"], woT, bw["datt"], M=M, N=D, K=D, concurrency=dxc)
         ops.attention_bwd(Lt["qkv"], bw["datt"], Lt["att"], Lt["lse"], bw["dvec"], bw["dqkv"], B, H, T, Tp,
                           cfg.head_dim ** -0.5)
-        o = model.flat_offsets[tl + "self_attn.q_proj.weight"]
-        g_wqkv = model.flat_grad[o: o + 3 * D * D].view(3 * D, D)
-        ob = model.flat_offsets[tl + "self_attn.q_proj.bias"]
-        g_bqkv = model.flat_grad[ob: ob + 3 * D]
-        on_side(3, lambda: dW(bw["dqkv"], Lt["h1"], g_wqkv, 3 * D, D, M, Mp, g_bqkv, part="part2"))
-        wqkv = model.flat_bf16[o: o + 3 * D * D].view(3 * D, D)
+        g_wqkv, g_bqkv = _qkv_grads(model, i)
+        on_side(3, lambda: weight_grad(bw["dqkv"], Lt["h1"], g_wqkv, 3 * D, D, M, dwe, g_bqkv))
         if pre_wt is not None:
             wqkvT = pre_wt[tl + "qkv"]
         else:
             wqkvT = bw["wT"][: 3 * D * D].view(D, 3 * D)
-            ops.transpose_bf16(wqkv, wqkvT, 3 * D, D)
+            ops.transpose_bf16(model._wqkv(i), wqkvT, 3 * D, D)
         ops.gemm(ops.EPI_BIAS_BF16, bw["dqkv"], wqkvT, bw["dh"], M=M, N=D, K=3 * D, concurrency=dxc)
         if not goes_on:
             # everything below layer_norm1 is frozen: only its affine parameters need gradients
@@ -472,5 +482,4 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
             ops.embed_bwd(bw["dxm"], dU, G("backbone.embeddings.class_embedding"), pw["dE"], B, T, Tp, D)
             ops.pos_resample_bwd(dU, g_pos, cfg.native_grid, cfg.grid, D)
         ops.im2row_bf16(ws["img"], pw["patches"], B, cfg.image_size, cfg.patch_size)
-        patch_weight_grad(pw["dE"], pw["patches"], G("backbone.embeddings.patch_embedding.weight").view(D, cfg.patch_k), D, cfg.patch_k, Mh,
-                          scratch=dict(slab=bw["slab"], tA=bw["tAh"], tB=bw["tBh"]))
+        patch_weight_grad(pw["dE"], pw["patches"], G("backbone.embeddings.patch_embedding.weight").view(D, cfg.patch_k), D, cfg.patch_k, Mh, scratch=bw["dw_main"])

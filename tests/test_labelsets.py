@@ -79,18 +79,18 @@ def test_wide_layout_sizes():
 
 
 def test_slab_scratch_covers_the_prompt_gradient_product():
-    """The split-K slab must hold the wide head's [Qp, Dt] prompt-gradient product on either route of autograd.dW; 10 classes size it as before."""
+    """The split-K slab must hold the wide head's [Qp, Dt] prompt-gradient product on either route of autograd.weight_grad; 10 classes size it as before."""
     from owl_vit_object_detection_amd import autograd as A
     for cname in ("owlvit-base-patch16", "owlvit-large-patch14", "tiny", "small"):
         cfg = get_config(cname)
         D, I, Dt = cfg.hidden, cfg.mlp, cfg.text_dim
         before = max(A._split_k(a, b, 1 << 30) * a * b for a, b in [(3 * D, D), (D, D), (I, D), (D, I), (Dt, D), (32, Dt)])
-        assert A._slab_elems(cfg) == A._slab_elems(cfg, 32) == before
+        assert A._dw_sizes(cfg).slab == A._dw_sizes(cfg, 32).slab == before
         for C in (11, 80, 384):
             Qp = ops.wide_qp(C)
             need_nt = A._split_k(Qp, Dt, 1 << 30) * Qp * Dt
             need_tn = (256 // ((Qp // 256) * (Dt // 256))) * Qp * Dt if Dt % 256 == 0 else 0
-            assert A._slab_elems(cfg, Qp) >= max(need_nt, need_tn) and A._dw_slab_elems(Qp, Dt) >= max(need_nt, need_tn)
+            assert A._dw_sizes(cfg, Qp).slab >= max(need_nt, need_tn) and A._dw_plan(Qp, Dt).slab_elems >= max(need_nt, need_tn)
 
 
 def test_385_classes_are_refused_at_construction():
