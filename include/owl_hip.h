@@ -32,7 +32,7 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's).  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's); still 8, additive again: + owl_gemm_nt_plan and the OWL_GEMM_KERNEL_* ids (which kernels a GEMM call launches; host query).  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
 #define OWL_ABI_VERSION 8
 const char* owl_last_error(void);
@@ -54,6 +54,15 @@ int owl_abi_version(void);
  *       for callers that know nothing else is in flight: batch 1 / 2, one stream).  All give identical bits.  (8, 9, 5, 4: the round-1 four-phase ping-pong, the round-4 free-running and the four-wave experiments,
  *       OWL_TUNING builds only.)                                                                                                                   */
 int owl_gemm_nt_bf16(void* stream, int epi, const void* A, int64_t lda, int64_t a_rows, const void* W, int64_t ldw, int64_t w_rows, const float* bias, void* out, int64_t ldo, const float* resid, void* aux, int64_t ld_aux, int64_t M, int64_t N, int64_t K, float alpha, int splits, int64_t Tp, int tile);
+/* Which kernels the call above launches, asked without a device (host function; it runs the launch's own argument checks and its own planner):
+ * returns the number of steps, 1 or 2, with kernels[i] = OWL_GEMM_KERNEL_* and rows[i] = the rows of M that step computes (two steps: rows
+ * [0, rows[0]) on kernels[0], the rest on kernels[1]); <0 with owl_last_error() for arguments the launch refuses.  has_aux: would `aux` be
+ * non-NULL.  `kernels`, `rows`: HOST arrays of 2. */
+#define OWL_GEMM_KERNEL_SP128 0   /* single-phase 128 x 128 (gemm.hip) */
+#define OWL_GEMM_KERNEL_SP256 1   /* single-phase 256 x 256 (gemm.hip) */
+#define OWL_GEMM_KERNEL_PP2 2     /* two-phase ping-pong 256 x 256 (gemm_pp2.hip) */
+#define OWL_GEMM_KERNEL_PPH 3     /* half-height ping-pong 128 x 256 (gemm_pph.hip) */
+int owl_gemm_nt_plan(int epi, int64_t M, int64_t N, int64_t K, int64_t a_rows, int has_aux, int64_t Tp, int splits, int tile, int* kernels, int64_t* rows);
 /* epi 11 = split-K partial slabs out[split][M][ldo] (f32, no atomics); reduce them with owl_slab_reduce */
 int owl_gemm_effective_splits(int64_t K, int splits);
 /* f32 slab scratch of an epi-11 call (M, N, K, splits): bytes = owl_gemm_effective_splits(K, splits) * M * ldo * 4 (`bytes`: HOST pointer) */

@@ -1,7 +1,7 @@
 /*
  * Tuning / race-hunting switches of libowlhip -- NOT part of the product ABI.  They are process-global mutable state and
  * only exist when the library is built with OWL_TUNING=1 (owl-vit-object-detection_amd/csrc/build.sh); the default build
- * does not export them and `_lib.py` only binds them when OWL_TUNING=1 is set in the environment.  Used by tools/*.py.
+ * does not export them and `_lib.py` only binds them when OWL_TUNING=1 is set in the environment.  Used by the scripts of tools/.
  */
 #ifndef OWL_HIP_TUNING_H
 #define OWL_HIP_TUNING_H
@@ -42,6 +42,10 @@ int owl_attention_fwd_w64_bf16(void* stream, const void* q, const void* k, const
 int owl_gemm_fr_ablate(int a);
 int owl_gemm_fr_slots(int n);
 int owl_gemm_fr_block_width(int epi, int bw);
+/* kernel ids owl_gemm_nt_plan reports in a tuning build only, after OWL_GEMM_KERNEL_* of owl_hip.h: tiles 8 / 9 (and the transposing epilogue), 5, 4 */
+#define OWL_GEMM_KERNEL_PP4 4    /* four-phase ping-pong 256 x 256 (tools/experiments/csrc/gemm_pp.hip) */
+#define OWL_GEMM_KERNEL_FR 5     /* free-running 128 x 256 (gemm_fr.hip) */
+#define OWL_GEMM_KERNEL_W4 6     /* four-wave 256 x 256 (gemm_w4.hip) */
 #ifdef __cplusplus
 }
 #endif

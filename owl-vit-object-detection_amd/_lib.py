@@ -35,6 +35,11 @@ def header_abi_version(path: str = None) -> int:
     return int(m.group(1))
 
 
+def header_constants(prefix: str, path: str = None):
+    """{name without the prefix: value} of the header's `#define <prefix>NAME <integer>` lines."""
+    return {m.group(1): int(m.group(2)) for m in re.finditer(rf"^\s*#\s*define\s+{prefix}(\w+)\s+(\d+)", open(path or HEADER).read(), flags=re.M)}
+
+
 def parse_header(path: str = None):
     """-> {name: (restype, [(ctype_name, arg_name), ...])} for every prototype in the header."""
     src = open(path or HEADER).read()

@@ -141,8 +141,10 @@ def _bws(model, B):
 
 
 def _split_k(n_rows_out, n_cols_out, k):
-    """Split the (long) token contraction so that a dW GEMM gives every CU about one work item."""
-    t = 256 if (n_rows_out >= 512 and n_cols_out >= 256) else 128          # tile the C side picks (gemm.hip `launch`)
+    """Split the (long) token contraction so that a dW GEMM gives every CU about one work item.  A work-item heuristic of its own: `t` is NOT the
+    library's tile rule (gemm_plan.h, gemm_auto_big, also wants 48 tiles of 256 x 256), and the split counts, hence gradient bits and slab sizes, rest
+    on this arithmetic as it stands."""
+    t = 256 if (n_rows_out >= 512 and n_cols_out >= 256) else 128
     tiles = ((n_rows_out + t - 1) // t) * ((n_cols_out + t - 1) // t)
     slots = 256 if t == 256 else 512
     return max(1, min(k // 64, slots // tiles))

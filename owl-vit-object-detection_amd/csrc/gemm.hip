@@ -17,7 +17,7 @@
 //     16-byte chunk index XOR-swizzled by ((row>>1)&7) -- applied to the per-lane SOURCE address and again on
 //     the ds_read_b128 address -- which makes every ds_read_b128 lane group conflict-free;
 //   * blocks are remapped so that consecutive tiles of one A row-panel run on the same XCD (private L2).
-#include "gemm_common.h"
+#include "gemm_plan.h"
 #include <type_traits>
 
 static constexpr int BK = 64;
@@ -158,7 +158,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_nt_kernel(Gem
     // bf16-output epilogues on the 256-wide tile use the register path: element-wise math, pack, v_permlane32_swap
     // pairing -> 16-byte stores.  On gfx950 vmcnt counts stores too and is in-order, so the vmcnt(0) of the next K-step
     // drains this tile's 16 stores per wave before any new LDS-DMA can be consumed -- that drain (not the store issue
-    // itself) is the epilogue cost of this single-phase kernel; gemm_pp.hip removes most of it with counted waits.
+    // itself) is the epilogue cost of this single-phase kernel; gemm_pp2.hip removes most of it with counted waits.
     // Holding the packed outputs in registers to store them during the next tile was measured and rejected (spills).
     constexpr bool WIDE = (BM == 256) && (EPI == EPI_BIAS_BF16 || EPI == EPI_QGELU_BF16 || EPI == EPI_GELU_BF16 ||
                                           EPI == EPI_DQGELU_BF16 || EPI == EPI_DGELU_BF16 || EPI == EPI_TRANS_BF16);
@@ -297,27 +297,54 @@ static int launch_cfg(hipStream_t s, GemmP p, int splits) {
     return 0;
 }
 
+// The other kernels of the family; each launcher has a `switch` over the epilogues its kernel is instantiated for (gemm_plan.h: pp2_takes, pph_takes, ...)
+// and fails on any other: gemm_plan never sends it one.
+int owl_gemm_pp2_launch(hipStream_t s, int epi, const GemmP& p);                                                      // gemm_pp2.hip
+int owl_gemm_pph_launch(hipStream_t s, int epi, const GemmP& p);                                                      // gemm_pph.hip
+#ifdef OWL_TUNING                                                                                                     // tools/experiments/csrc/
 int owl_gemm_pp_launch(hipStream_t s, int epi, const GemmP& p, int slots_override, int persistent_on, int nostore);   // gemm_pp.hip
 int owl_gemm_w4_launch(hipStream_t s, int epi, const GemmP& p);                                                       // gemm_w4.hip
-int owl_gemm_pph_launch(hipStream_t s, int epi, const GemmP& p);                                                      // gemm_pph.hip
-int owl_gemm_pp2_launch(hipStream_t s, int epi, const GemmP& p);                                                      // gemm_pp2.hip
 int owl_gemm_fr_launch(hipStream_t s, int epi, const GemmP& p);                                                       // gemm_fr.hip
+#endif
 
 template <int EPI>
-static int launch(hipStream_t s, const GemmP& p, int splits, int g_force_tile = 0) {
-    // 256-wide tiles only when they give the chip enough work items (batch-1 out-proj is 10 x 3 of them: the 128x128
-    // kernel's 114 tiles finish sooner)
-    const int64_t t256 = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-    const bool big = g_force_tile ? (g_force_tile == 256 || g_force_tile == 8 || g_force_tile == 9) : (p.M >= 512 && p.N >= 256 && t256 >= 48);
-    if (big) return launch_cfg<EPI, 256, 256, 128, 64>(s, p, splits);
+static int launch(hipStream_t s, const GemmP& p, int splits, int kernel) {      // kernel: OWL_GEMM_KERNEL_SP256 / _SP128 (gemm_single_phase)
+    if (kernel == OWL_GEMM_KERNEL_SP256) return launch_cfg<EPI, 256, 256, 128, 64>(s, p, splits);
     return launch_cfg<EPI, 128, 128, 64, 64>(s, p, splits);
 }
 
-OWL_API int owl_gemm_nt_bf16(void* stream, int epi, const void* A, int64_t lda, int64_t a_rows, const void* W,
-                                int64_t ldw, int64_t w_rows, const float* bias, void* out, int64_t ldo,
-                                const float* resid, void* aux, int64_t ld_aux, int64_t M, int64_t N, int64_t K,
-                                float alpha, int splits, int64_t Tp, int tile) {
-    OWL_CHECK_ARG(A && W && out, "owl_gemm_nt_bf16: null pointer");
+// One step of a plan: `kernel` on the rows `p` describes.
+static int launch_step(hipStream_t s, int kernel, int epi, GemmP p, int splits) {
+    switch (kernel) {
+        case OWL_GEMM_KERNEL_PP2: return owl_gemm_pp2_launch(s, epi, p);
+        case OWL_GEMM_KERNEL_PPH: return owl_gemm_pph_launch(s, epi, p);
+#ifdef OWL_TUNING
+        case OWL_GEMM_KERNEL_PP4: return owl_gemm_pp_launch(s, epi, p, g_debug_slots, g_persistent, g_debug_nostore);
+        case OWL_GEMM_KERNEL_FR: return owl_gemm_fr_launch(s, epi, p);
+        case OWL_GEMM_KERNEL_W4: return owl_gemm_w4_launch(s, epi, p);
+#endif
+    }
+    switch (epi) {                                       // the single-phase kernels (splits > 1: the slab / atomic epilogues only, gemm_nt_check)
+        case EPI_BIAS_BF16: return launch<EPI_BIAS_BF16>(s, p, splits, kernel);
+        case EPI_QGELU_BF16: return launch<EPI_QGELU_BF16>(s, p, splits, kernel);
+        case EPI_GELU_BF16: return launch<EPI_GELU_BF16>(s, p, splits, kernel);
+        case EPI_RESID_F32: return launch<EPI_RESID_F32>(s, p, splits, kernel);
+        case EPI_ACC_F32: p.resid = (const float*)p.out; return launch<EPI_ACC_F32>(s, p, splits, kernel);
+        case EPI_F32: return launch<EPI_F32>(s, p, splits, kernel);
+        case EPI_SLAB_F32: return launch<EPI_SLAB_F32>(s, p, splits, kernel);
+        case EPI_DQGELU_BF16: return launch<EPI_DQGELU_BF16>(s, p, splits, kernel);
+        case EPI_DGELU_BF16: return launch<EPI_DGELU_BF16>(s, p, splits, kernel);
+#ifdef OWL_TUNING
+        case EPI_ATOMIC_F32: return launch<EPI_ATOMIC_F32>(s, p, splits, kernel);
+        case EPI_TRANS_BF16: return launch<EPI_TRANS_BF16>(s, p, splits, kernel);
+#endif
+        default: owl_set_error("owl_gemm_nt_bf16: no single-phase kernel for epilogue %d (gemm_nt_check let it through)", epi); return -1;
+    }
+}
+
+// The argument checks of owl_gemm_nt_bf16 on everything a plan depends on, shared with owl_gemm_nt_plan: the query refuses what the launch refuses.
+// `splits` leaves as the number of K ranges the call really uses (owl_gemm_effective_splits).
+static int gemm_nt_check(int epi, int64_t M, int64_t N, int64_t K, int64_t a_rows, bool has_aux, int64_t Tp, int& splits, int tile) {
 #ifdef OWL_TUNING
     OWL_CHECK_ARG(tile == 0 || tile == 128 || tile == 256 || tile == 8 || tile == 9 || tile == 4 || tile == 7 || tile == 5 || tile == 6, "owl_gemm_nt_bf16: tile must be 0 (auto), 6, 128, 256, 7 (or, tuning builds, 8, 9, 5, 4)");
 #else
@@ -326,13 +353,31 @@ OWL_API int owl_gemm_nt_bf16(void* stream, int epi, const void* A, int64_t lda, 
     OWL_CHECK_ARG(epi != EPI_TRANS_BF16 && epi != EPI_ATOMIC_F32, "owl_gemm_nt_bf16: epilogues 5 (f32 atomics) and 6 (per-head transposed) exist only in an OWL_TUNING build "
                                                                     "(the train path uses split-K slabs and reads V row-major)");
 #endif
-    const bool want_half = tile == 6;          // 6 = automatic + "half-height tiles if the whole problem is at most half a round" (see below)
-    const int g_force_tile = want_half ? 0 : tile;
+    OWL_CHECK_ARG(epi >= EPI_BIAS_BF16 && epi <= EPI_SLAB_F32 && epi != EPI_PATCH_F32,
+                  "owl_gemm_nt_bf16: unknown epilogue %d (7 and 12, the patch gathers, run through owl_patch_embed_bf16 only)", epi);
     OWL_CHECK_ARG(K > 0 && K % BK == 0, "owl_gemm_nt_bf16: K=%lld must be a positive multiple of 64", (long long)K);
     OWL_CHECK_ARG(M > 0 && N > 0 && N % 8 == 0, "owl_gemm_nt_bf16: bad M=%lld N=%lld (N %% 8 == 0)", (long long)M, (long long)N);
-    OWL_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0, "owl_gemm_nt_bf16: lda/ldw must be multiples of 8 elements");
-    OWL_CHECK_ARG(a_rows > 0 && w_rows > 0, "owl_gemm_nt_bf16: a_rows / w_rows");
+    OWL_CHECK_ARG(a_rows > 0, "owl_gemm_nt_bf16: a_rows / w_rows");
     OWL_CHECK_ARG(splits >= 1, "owl_gemm_nt_bf16: splits");
+    splits = owl_gemm_effective_splits(K, splits);
+    OWL_CHECK_ARG(splits == 1 || epi == EPI_ATOMIC_F32 || epi == EPI_SLAB_F32, "owl_gemm_nt_bf16: split-K needs the slab epilogue");
+    OWL_CHECK_ARG(epi != EPI_TRANS_BF16 || (Tp > 0 && Tp % 4 == 0 && N % 64 == 0), "EPI_TRANS_BF16: Tp %% 4, N %% 64");
+    OWL_CHECK_ARG(epi != EPI_DQGELU_BF16 || has_aux, "EPI_DQGELU needs aux");
+    OWL_CHECK_ARG(epi != EPI_DGELU_BF16 || has_aux, "EPI_DGELU needs aux");
+    return 0;
+}
+
+OWL_API int owl_gemm_nt_bf16(void* stream, int epi, const void* A, int64_t lda, int64_t a_rows, const void* W,
+                                int64_t ldw, int64_t w_rows, const float* bias, void* out, int64_t ldo,
+                                const float* resid, void* aux, int64_t ld_aux, int64_t M, int64_t N, int64_t K,
+                                float alpha, int splits, int64_t Tp, int tile) {
+    OWL_CHECK_ARG(A && W && out, "owl_gemm_nt_bf16: null pointer");
+    if (const int rc = gemm_nt_check(epi, M, N, K, a_rows, aux != nullptr, Tp, splits, tile)) return rc;
+    OWL_CHECK_ARG(lda % 8 == 0 && ldw % 8 == 0, "owl_gemm_nt_bf16: lda/ldw must be multiples of 8 elements");
+    OWL_CHECK_ARG(w_rows > 0, "owl_gemm_nt_bf16: a_rows / w_rows");
+    OWL_CHECK_ARG(epi != EPI_RESID_F32 || resid, "EPI_RESID_F32 needs resid");
+    OWL_CHECK_ARG(epi != EPI_ATOMIC_F32 || !bias, "atomic epilogue takes no bias");
+    OWL_CHECK_ARG(epi != EPI_SLAB_F32 || !bias, "slab epilogue takes no bias");
     GemmP p{};
     p.A = (const bf16_t*)A; p.lda = lda; p.a_rows = a_rows;
     p.W = (const bf16_t*)W; p.ldw = ldw; p.w_rows = w_rows;
@@ -340,107 +385,28 @@ OWL_API int owl_gemm_nt_bf16(void* stream, int epi, const void* A, int64_t lda, 
     p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.Tp = Tp;
     p.slab_stride = M * ldo;
     const int nk = (int)(K / BK);
-    if (splits > nk) splits = nk;
-    p.kt_per_split = (nk + splits - 1) / splits;
-    splits = (nk + p.kt_per_split - 1) / p.kt_per_split;
-    hipStream_t s = (hipStream_t)stream;
-    const bool split_ok = (epi == EPI_ATOMIC_F32 || epi == EPI_SLAB_F32);
-    OWL_CHECK_ARG(splits == 1 || split_ok, "owl_gemm_nt_bf16: split-K needs the slab epilogue");
-    // bf16-output epilogues on big problems run the ping-pong schedule (gemm_pp.hip): 13-26 % faster, bit-identical
-#ifdef OWL_TUNING
-    if (g_force_tile == 4 && K >= 128) {                 // experimental four-wave kernel (tuning builds only)
-        const int rc = owl_gemm_w4_launch(s, epi, p);
-        if (rc <= 0) return rc;
+    p.kt_per_split = (nk + splits - 1) / splits;         // (`splits` is the effective count: it gives back the K-tiles per split it was formed from)
+    const GemmPlan plan = gemm_plan(epi, M, N, K, a_rows, tile, g_debug_nostore != 0);
+    int64_t row0 = 0;
+    for (int i = 0; i < plan.n; row0 += plan.rows[i++]) {
+        GemmP q = p;                                     // rows [row0, row0 + plan.rows[i]) of the problem
+        q.M = plan.rows[i];
+        q.a_rows = i + 1 < plan.n ? q.M : a_rows - row0;
+        q.A = p.A + row0 * lda;
+        q.out = (bf16_t*)out + row0 * ldo;               // (a plan of two steps ends on the half-height kernel: a bf16 output)
+        if (aux) q.aux = (bf16_t*)aux + row0 * ld_aux;
+        if (const int rc = launch_step((hipStream_t)stream, plan.kernel[i], epi, q, splits)) return rc;
     }
-#endif
-#ifdef OWL_TUNING
-    if (g_force_tile == 5 && splits == 1) {              // round-4 experiment (tuning builds only): free-running 128 x 256 workgroups, two per CU (gemm_fr.hip)
-        const int rc = owl_gemm_fr_launch(s, epi, p);
-        if (rc <= 0) return rc;
-    }
-#endif
-    if (g_force_tile == 7 && K >= 128) {                 // two-phase ping-pong kernel on the whole problem (A/B; falls through for other epilogues)
-        const int rc = owl_gemm_pp2_launch(s, epi, p);
-        if (rc <= 0) return rc;
-    }
-    // the ping-pong kernel for this epilogue: the two-phase schedule (gemm_pp2.hip) where it exists (bias / quick-GELU: +3..9 % on the model's
-    // shapes, bit-identical), the four-phase one (gemm_pp.hip) otherwise or when asked for by tile = 8 / 9
-    auto pp_launch = [&](const GemmP& q) -> int {
-        if (g_force_tile == 0 && g_debug_nostore == 0) {
-            const int rc = owl_gemm_pp2_launch(s, epi, q);
-            if (rc <= 0) return rc;
-        }
-#ifdef OWL_TUNING
-        return owl_gemm_pp_launch(s, epi, q, g_debug_slots, g_persistent, g_debug_nostore);      // the four-phase kernel (tile 8 / 9, the transposing epilogue)
-#else
-        return 1;                    // not a two-phase epilogue: the single-phase kernel below
-#endif
-    };
-    const bool pp_auto = (g_force_tile == 0 && M >= 512 && N >= 256 && ((M + 255) / 256) * ((N + 255) / 256) >= 48);
-    if ((g_force_tile == 8 || g_force_tile == 9 || pp_auto) && K >= 128 && (epi != EPI_TRANS_BF16 || (Tp > 0 && Tp % 4 == 0 && N % 64 == 0)) &&
-        ((epi != EPI_DQGELU_BF16 && epi != EPI_DGELU_BF16) || aux)) {
-        // Tile quantisation: tm x tn tiles of 256 x 256 on 256 workgroups = full_rounds whole rounds + a remainder round that keeps
-        // only `rem` CUs busy (N = 768: 867 tiles = 3.39 -> 4 rounds).  When the remainder fits one round of HALF-height tiles the
-        // whole rounds go to the 256 x 256 ping-pong kernel and the remaining row tiles to the 128 x 256 variant (gemm_pph.hip):
-        // one round of ~0.56 tile times instead of a whole one.  Same K order and epilogue: bit-identical.
-        // Measured (tools/gemm_remainder_bench.py, same-process A/B at M = 73 984): +3.6 % fc2 (K = 3072), +2.5 % dX (K = 2304), +4.2 % box-head
-        // dense (GELU epilogue), +0.8 % out-proj (K = 768); nothing for wide outputs (QKV N = 2304: -0.1 %, fc1: does not fit one round), where
-        // the half-height tiles -- latency-bound, ~0.85 of a full tile's time, not 0.56 -- only just pay for the second launch.  Hence the
-        // automatic rule: narrow outputs only (N <= 1024); tile = 9 forces the split wherever it fits, tile = 8 never splits.
-        // tile = 6 -- small problems (the reference's own batch size of 1: QKV = 90 tiles, fc1 = 120 on 256 CUs): no more 256 x 256 tiles than HALF the CUs ->
-        // every tile goes out as two half-height tiles (gemm_pph.hip), one partial round of ~0.85 tile times on twice the CUs.  Same K order and epilogue:
-        // bit-identical.  Asked for by the CALLER, who knows what else is in flight: with two sub-batch streams the other stream's tiles already fill the idle
-        // CUs and the half-height split loses (forward batch 8: -2.7 %; alone: +3.3 % / +4.5 % on the batch-1 train step / forward, profiles/r05_small_batch.md).
-        if (want_half && a_rows >= M && 2 * ((M + 255) / 256) * ((N + 255) / 256) <= NUM_CUS) {
-            const int rc = owl_gemm_pph_launch(s, epi, p);
-            if (rc <= 0) return rc;      // 1 = epilogue not handled by the half-height kernel: the 256 x 256 kernel below
-        }
-        if ((g_force_tile == 9 || (g_force_tile == 0 && N <= 1024)) && epi != EPI_TRANS_BF16 && epi != EPI_F32 && epi != EPI_ACC_F32 && a_rows >= M) {
-            const int64_t tm = (M + 255) / 256, tn = (N + 255) / 256, items = tm * tn;
-            const int64_t full_rounds = items / NUM_CUS;
-            const int64_t tm_main = (full_rounds * NUM_CUS) / tn;
-            const int64_t rem_tiles = (tm - tm_main) * tn;
-            if (full_rounds >= 1 && tm_main >= 1 && rem_tiles > 0 && 2 * rem_tiles <= NUM_CUS && items - full_rounds * NUM_CUS > 0) {
-                const int64_t M_main = tm_main * 256;
-                GemmP pm = p;
-                pm.M = M_main; pm.a_rows = M_main;
-                int rc = pp_launch(pm);
-                if (rc < 0) return rc;
-                if (rc == 0) {
-                    GemmP pr = p;
-                    pr.A = p.A + M_main * lda; pr.a_rows = a_rows - M_main; pr.M = M - M_main;
-                    pr.out = (void*)((bf16_t*)p.out + M_main * ldo);
-                    if (p.aux) pr.aux = (void*)((bf16_t*)p.aux + M_main * ld_aux);
-                    rc = owl_gemm_pph_launch(s, epi, pr);
-                    if (rc <= 0) return rc;
-                    // (epilogue not handled by the half-height kernel: finish the remainder rows with the 256 x 256 kernel)
-                    return pp_launch(pr);
-                }
-            }
-        }
-        const int rc = pp_launch(p);
-        if (rc <= 0) return rc;      // 1 = epilogue not handled there: fall through
-    }
-    switch (epi) {
-        case EPI_BIAS_BF16: return launch<EPI_BIAS_BF16>(s, p, 1, g_force_tile);
-        case EPI_QGELU_BF16: return launch<EPI_QGELU_BF16>(s, p, 1, g_force_tile);
-        case EPI_GELU_BF16: return launch<EPI_GELU_BF16>(s, p, 1, g_force_tile);
-        case EPI_RESID_F32: OWL_CHECK_ARG(resid, "EPI_RESID_F32 needs resid"); return launch<EPI_RESID_F32>(s, p, 1, g_force_tile);
-        case EPI_ACC_F32: p.resid = (const float*)out; return launch<EPI_ACC_F32>(s, p, 1, g_force_tile);
-        case EPI_F32: return launch<EPI_F32>(s, p, 1, g_force_tile);
-#ifdef OWL_TUNING
-        case EPI_ATOMIC_F32: OWL_CHECK_ARG(!bias, "atomic epilogue takes no bias"); return launch<EPI_ATOMIC_F32>(s, p, splits, g_force_tile);
-#endif
-        case EPI_SLAB_F32: OWL_CHECK_ARG(!bias, "slab epilogue takes no bias"); return launch<EPI_SLAB_F32>(s, p, splits, g_force_tile);
-#ifdef OWL_TUNING
-        case EPI_TRANS_BF16:
-            OWL_CHECK_ARG(Tp > 0 && Tp % 4 == 0 && N % 64 == 0, "EPI_TRANS_BF16: Tp %% 4, N %% 64");
-            return launch<EPI_TRANS_BF16>(s, p, 1, g_force_tile);
-#endif
-        case EPI_DQGELU_BF16: OWL_CHECK_ARG(aux, "EPI_DQGELU needs aux"); return launch<EPI_DQGELU_BF16>(s, p, 1, g_force_tile);
-        case EPI_DGELU_BF16: OWL_CHECK_ARG(aux, "EPI_DGELU needs aux"); return launch<EPI_DGELU_BF16>(s, p, 1, g_force_tile);
-        default: owl_set_error("owl_gemm_nt_bf16: unknown epilogue %d", epi); return -1;
-    }
+    return 0;
+}
+
+OWL_API int owl_gemm_nt_plan(int epi, int64_t M, int64_t N, int64_t K, int64_t a_rows, int has_aux, int64_t Tp, int splits, int tile, int* kernels,
+                             int64_t* rows) {
+    OWL_CHECK_ARG(kernels && rows, "owl_gemm_nt_plan: null pointer");
+    if (const int rc = gemm_nt_check(epi, M, N, K, a_rows, has_aux != 0, Tp, splits, tile)) return rc;
+    const GemmPlan plan = gemm_plan(epi, M, N, K, a_rows, tile, g_debug_nostore != 0);
+    for (int i = 0; i < plan.n; i++) { kernels[i] = plan.kernel[i]; rows[i] = plan.rows[i]; }
+    return plan.n;
 }
 
 // number of split-K slabs the call above will actually write for (K, splits): callers size the slab buffer with it
@@ -558,7 +524,7 @@ __global__ __launch_bounds__(256) void im2row_kernel(const bf16_t* __restrict__ 
 // `scratch` (bf16 [B*P (row-padded to 128), Kg]) is needed only when a single-phase reference kernel (tile = 256 / 128, or a problem too small for the ping-pong
 // kernel) meets a patch size that is not 2^n: it then receives an explicit im2row in the same K order (identical bits).
 static bool patch_embed_takes_pp2(int64_t M, int64_t D, int64_t Kg, int tile) {
-    return (tile == 7 || (tile == 0 && M >= 512 && D >= 256 && ((M + 255) / 256) * ((D + 255) / 256) >= 48)) && Kg >= 128;
+    return (tile == 7 || (tile == 0 && gemm_auto_big(M, D))) && Kg >= 128;
 }
 
 // Bytes of the `scratch` argument of owl_patch_embed_bf16 for this problem and kernel choice: 0 when the chosen kernel gathers from the image itself (every 2^n
@@ -597,12 +563,12 @@ OWL_API int owl_patch_embed_bf16(void* stream, const void* image_bf16, const voi
     p.nsplit = 1;
     // big problems: the two-phase ping-pong kernel (same bits); tile = 256 / 128 pins the single-phase kernels, 7 the ping-pong one
     if (patch_embed_takes_pp2(p.M, D, Kg, tile)) return owl_gemm_pp2_launch((hipStream_t)stream, EPI_PATCH_F32, p);
-    if (pow2) return launch<EPI_PATCH_F32>((hipStream_t)stream, p, 1, tile);           // (the single-phase kernels gather 2^n patch rows themselves)
+    if (pow2) return launch<EPI_PATCH_F32>((hipStream_t)stream, p, 1, gemm_single_phase(p.M, D, tile));           // (the single-phase kernels gather 2^n patch rows themselves)
     OWL_CHECK_ARG(scratch, "owl_patch_embed_bf16: patch size %lld on a single-phase kernel (tile %d, or a problem too small for the ping-pong kernel) needs the im2row scratch buffer",
                   (long long)ps, tile);
     hipLaunchKernelGGL(im2row_kernel, dim3((unsigned)(B * P)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)image_bf16, (bf16_t*)scratch,
                        B, (int)S, (int)ps, (int)psp, (int)G, (int)K, (int)Kg);
     OWL_LAUNCH_CHECK();
     p.A = (const bf16_t*)scratch; p.lda = Kg;
-    return launch<EPI_PATCHM_F32>((hipStream_t)stream, p, 1, tile);
+    return launch<EPI_PATCHM_F32>((hipStream_t)stream, p, 1, gemm_single_phase(p.M, D, tile));
 }

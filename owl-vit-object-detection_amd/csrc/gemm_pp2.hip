@@ -543,7 +543,7 @@ OWL_API int owl_gemm_pp2_trace_tile(int n) { g_pp2_trace_tile = n; return 0; }
 OWL_API int owl_gemm_pp2_trace_ktile(int n) { g_pp2_trace_kt = n; return 0; }
 #endif
 
-// called from gemm.hip's dispatcher; returns 1 if this variant does not handle `epi`
+// called from gemm.hip for the steps gemm_plan gives this kernel (and for the patch embedding); the cases are pp2_takes (gemm_plan.h)
 int owl_gemm_pp2_launch(hipStream_t s, int epi, const GemmP& p) {
 #ifdef OWL_TUNING
     if (g_pp2_trace && epi == EPI_BIAS_BF16) {
@@ -574,6 +574,6 @@ int owl_gemm_pp2_launch(hipStream_t s, int epi, const GemmP& p) {
         case EPI_ACC_F32: return launch_pp2<EPI_ACC_F32>(s, p);       // dfeats += (box head)
         case EPI_PATCH_F32: return launch_pp2<EPI_PATCH_F32>(s, p);   // patch embedding, A gathered from the image
         case EPI_PATCHM_F32: return launch_pp2<EPI_PATCHM_F32>(s, p); // ... from an explicit im2row matrix (L/14)
-        default: return 1;                                            // (the transposing epilogue stays on the four-phase kernel)
+        default: owl_set_error("owl_gemm_pp2_launch: epilogue %d is not one of pp2_takes (planner and launcher disagree)", epi); return -1;
     }
 }

@@ -1,11 +1,11 @@
-// Half-height (128 x 256 x 64) ping-pong GEMM tile for the REMAINDER ROUND of the 256 x 256 ping-pong kernel (gemm_pp.hip).
+// Half-height (128 x 256 x 64) ping-pong GEMM tile for the REMAINDER ROUND of the 256 x 256 ping-pong kernel (gemm_pp2.hip).
 //
 // Why: the model's N = 768 GEMMs (out-proj, fc2, their dX forms, the box head) have 289 x 3 = 867 tiles of 256 x 256 for 256
-// workgroups = 3.39 rounds, executed as 4: the last round keeps 99 of 256 CUs busy.  The dispatcher (gemm.hip) therefore gives the
+// workgroups = 3.39 rounds, executed as 4: the last round keeps 99 of 256 CUs busy.  The planner (gemm_plan.h, gemm_plan) therefore gives the
 // whole rounds to the 256 x 256 kernel and the remaining row tiles to THIS kernel, split into half-height tiles: 99 tiles become 198
 // workgroups of 128 x 256, one round of about 0.56 tile times instead of a whole one (3.39 -> 3.56 instead of 4 rounds).
 //
-// Same operands, same LDS image (LDS-DMA, 16-byte chunk XOR swizzle), same MFMA shape and K order, same epilogue code as gemm_pp.hip
+// Same operands, same LDS image (LDS-DMA, 16-byte chunk XOR swizzle), same MFMA shape and K order, same epilogue code as gemm_pp2.hip
 // -> bit-identical outputs (tests/test_determinism_gpu.py).  Schedule: 8 waves = two groups of four (group g = output rows g*64..+64,
 // wave wc = 64-column slice; every SIMD hosts one wave of each group); a K-tile is TWO quadrant phases (64x32 of the wave's 64x64
 // output: 8 MFMAs of 32x32x16), each split by barriers into a LOAD half and an MFMA half; group 1 runs one barrier behind group 0, so
@@ -205,7 +205,7 @@ static int launch_pph(hipStream_t s, GemmP p) {
     return 0;
 }
 
-// called from gemm.hip's dispatcher for the remainder rows; returns 1 if this variant does not handle `epi`
+// called from gemm.hip for the steps gemm_plan gives this kernel (remainder rows, or a small problem under tile 6); the cases are pph_takes (gemm_plan.h)
 int owl_gemm_pph_launch(hipStream_t s, int epi, const GemmP& p) {
     switch (epi) {
         case EPI_BIAS_BF16: return launch_pph<EPI_BIAS_BF16>(s, p);
@@ -213,6 +213,6 @@ int owl_gemm_pph_launch(hipStream_t s, int epi, const GemmP& p) {
         case EPI_DQGELU_BF16: return launch_pph<EPI_DQGELU_BF16>(s, p);
         case EPI_GELU_BF16: return launch_pph<EPI_GELU_BF16>(s, p);
         case EPI_DGELU_BF16: return launch_pph<EPI_DGELU_BF16>(s, p);
-        default: return 1;
+        default: owl_set_error("owl_gemm_pph_launch: epilogue %d is not one of pph_takes (planner and launcher disagree)", epi); return -1;
     }
 }

@@ -20,7 +20,7 @@ attention_reference.py:24-25); "1 ulp" of v_exp_f32 / v_rcp_f32 is a relative 2 
 normal of f32 and bf16: the MFMAs, v_exp / v_rcp and the bf16 conversion do not keep denormals.
 
  accumulation.  The products of two bf16 are exact in f32; the kernels add them with v_mfma_f32_32x32x16_bf16, 16 products per instruction
-   into one accumulator, K / 16 instructions in a row, K-tile after K-tile (gemm.hip:212-226, gemm_pp2.hip / gemm_pph.hip: same order).
+   into one accumulator, K / 16 instructions in a row, K-tile after K-tile (gemm.hip, gemm_nt_kernel's main loop; gemm_pp2.hip / gemm_pph.hip: same order).
    ASSUMPTION 1: the rounding of the MFMA's internal adds is not documented as round-to-nearest, so every add is budgeted at 2 f (truncation)
    and the order of the 16 products inside one instruction is taken as unknown.  A product then passes at most 16 adds inside its own
    instruction (15 among the products, 1 onto the accumulator) and one add per later instruction:
@@ -57,7 +57,7 @@ normal of f32 and bf16: the MFMAs, v_exp / v_rcp and the bf16 conversion do not 
    Phi = fma(0.5, +-erf_abs, 0.5): 0.5 d_erf + f Phi;  a phi = fl(fl(a k) e~): |a phi| (3 f + re) (1 + f);  the sum: f |d|:
        d_eval = 0.5 d_erf + f Phi + |a phi| ((1 + 3 f)(1 + re) - 1) + f |d| + (|a| + 1) T
    out = fl(v d~):  E = |d| E_pre + (|pre| + E_pre) d_eval + f (|pre d| + ...) + T.
- slab path (EPI_SLAB_F32 + owl_slab_reduce, gemm.hip:461-480): slab s is bounded with n_acc of its own K range; the reduce adds nsplit
+ slab path (EPI_SLAB_F32 + owl_slab_reduce, gemm.hip: slab_reduce_kernel): slab s is bounded with n_acc of its own K range; the reduce adds nsplit
    (+ 1 with accumulate) values in f32: gamma(nsplit + 1) (sum_s (|slab_s| + tol_s) + |out_old|) on top of sum_s tol_s.
 
 `check(name, got, ref, tol)` tests every element (no exclusions), `untouched` every element outside [0, M) x [0, N) bit for bit.
@@ -117,7 +117,7 @@ def bf16_round(x):
 
 
 def split_ranges(K, splits):
-    """K ranges of the slabs owl_gemm_nt_bf16 writes for (K, splits) (gemm.hip:342-345)."""
+    """K ranges of the slabs owl_gemm_nt_bf16 writes for (K, splits) (gemm.hip, owl_gemm_effective_splits)."""
     nk = K // BK
     splits = max(1, min(splits, nk))
     per = (nk + splits - 1) // splits
@@ -492,16 +492,16 @@ def emulate(epi, A, W, bias=None, alpha=1.0, resid=None, aux_in=None, splits=1, 
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-# the dispatcher's conditions (owl_gemm_nt_bf16, gemm.hip:362-423) and the case set shared by the CPU and the GPU test
+# the planner's conditions (gemm_plan.h, gemm_plan: what owl_gemm_nt_bf16 launches), restated, and the case set shared by the CPU and the GPU test
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 NUM_CUS = 256
-PP2_EPIS = (EPI_BIAS, EPI_QGELU, EPI_DQGELU, EPI_GELU, EPI_DGELU, EPI_F32, EPI_ACC)      # gemm_pp2.hip:567-577
-PPH_EPIS = (EPI_BIAS, EPI_QGELU, EPI_DQGELU, EPI_GELU, EPI_DGELU)                        # gemm_pph.hip:209-217
+PP2_EPIS = (EPI_BIAS, EPI_QGELU, EPI_DQGELU, EPI_GELU, EPI_DGELU, EPI_F32, EPI_ACC)      # gemm_plan.h, pp2_takes (less the patch gathers)
+PPH_EPIS = (EPI_BIAS, EPI_QGELU, EPI_DQGELU, EPI_GELU, EPI_DGELU)                        # gemm_plan.h, pph_takes
 
 
 def gemm_split(M, N, tile):
     """M_main of the automatic kernel choice (whole rounds of 256 x 256 tiles + one round of half-height remainder tiles), or None: the
-    arithmetic of test_kernel_model_forms_gpu.py::_gemm_split and gemm.hip:398-404."""
+    arithmetic of gemm_plan.h, gemm_whole_round_rows, restated."""
     if tile != 0 or N > 1024:
         return None
     tm, tn = (M + 255) // 256, (N + 255) // 256
@@ -516,7 +516,8 @@ def gemm_split(M, N, tile):
 
 def dispatch_path(epi, M, N, K, tile, a_rows=None):
     """[(kernel, rows)] the shipped library launches: 'pp2' two-phase 256 x 256 (gemm_pp2.hip), 'pph' half-height 128 x 256 (gemm_pph.hip), 'sp256' /
-    'sp128' the single-phase kernels of gemm.hip."""
+    'sp128' the single-phase kernels of gemm.hip.  The independent restatement of gemm_plan.h's gemm_plan: tests/test_gemm_plan.py holds the
+    library's own answer (library_path) to it."""
     a_rows = M if a_rows is None else a_rows
     want_half = tile == 6
     ft = 0 if want_half else tile
@@ -536,9 +537,25 @@ def dispatch_path(epi, M, N, K, tile, a_rows=None):
     return [("sp256" if big else "sp128", M)]
 
 
+_PLAN = {}
+
+
+def library_path(epi, M, N, K, tile, a_rows=None, has_aux=1, Tp=0, splits=1):
+    """[(kernel, rows)] in dispatch_path's names, ASKED of the library: owl_gemm_nt_plan runs the argument checks and the planner of the launch itself
+    (host only, no device).  Raises OwlLibError with the library's message for arguments the launch refuses."""
+    from owl_vit_object_detection_amd import _lib
+    if not _PLAN:
+        import ctypes
+        _PLAN.update(fn=_lib.load().owl_gemm_nt_plan, kernels=(ctypes.c_int * 2)(), rows=(ctypes.c_int64 * 2)(),
+                     names={v: k.lower() for h in (_lib.HEADER, _lib.TUNING_HEADER) for k, v in _lib.header_constants("OWL_GEMM_KERNEL_", h).items()})
+    n = _PLAN["fn"](epi, M, N, K, M if a_rows is None else a_rows, has_aux, Tp, splits, tile, _PLAN["kernels"], _PLAN["rows"])
+    if n < 0:
+        raise _lib.OwlLibError(f"owl_gemm_nt_plan failed (rc={n}): {_lib.last_error()}")
+    return [(_PLAN["names"][_PLAN["kernels"][i]], _PLAN["rows"][i]) for i in range(n)]
+
+
 def sample_rows(M, M_main):
-    """Rows of the one tall case: the first tile, one row of every 128-row band (offset varying), both sides of M_main, the last rows (the rule of
-    test_kernel_model_forms_gpu.py::_gemm_rows)."""
+    """Rows to check of a tall problem: the first tile, one row of every 128-row band (offset varying), both sides of M_main, the last rows."""
     rows = {0, 1, 127, 128, 255, M - 1, M - 2, M - 129}
     rows.update(b * 128 + (b * 37) % 128 for b in range((M + 127) // 128))
     if M_main is not None:

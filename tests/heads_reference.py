@@ -61,7 +61,7 @@ rnd are layernorm_reference.py:20,303-326.
  box_final backward (backward.hip:620-685): _V through dlin, dpre = (dlin s)(1 - s), dh1 (4 products, 3 adds), o = dh1 dgelu_erf_f(u1) with
    gemm_reference.dgelu_eval as the evaluation error of dgelu_erf_f (its Assumption on A&S 7.1.26 included); du1 = bf16(o).
    Row reductions, adds counted as the source orders them: inside a block rows in order: rpb adds (rpb = clamp(ceil(rows / 512), 8, 64));
-   db2: each row sits in one thread (rpb <= 64 < 256): wave_sum (6) + four waves in order (3); owl_slab_reduce_impl (gemm.hip:517-526):
+   db2: each row sits in one thread (rpb <= 64 < 256): wave_sum (6) + four waves in order (3); owl_slab_reduce_impl (gemm.hip):
    nblk >= 128 (and n / 4 <= 8192: always here) -> tall_reduce_kernel: lane g adds slabs g, g + 8, ... in order (ceil(nblk / 8)), then old + the 8
    lane sums in order (8); else slab_reduce_kernel: old + slab 0 + slab 1 ... in order (nblk):   `n_reduce(nblk)`
        tol = gamma(n) (sum_rows (|term| + E_term) + |old|) + sum_rows E_term + T,   n = rpb + n_reduce (dW2, colsum), 9 + n_reduce (db2).

@@ -57,7 +57,7 @@ def test_no_process_global_setters_in_the_product_abi(built):
             assert not hasattr(lib, name), f"{name} exported by the default build"
     # every op that needs device scratch has a size query
     for q in ("owl_postprocess_workspace", "owl_box_final_bwd_blocks", "owl_gemm_effective_splits", "owl_gemm_tn_slab_workspace_bytes",
-              "owl_attention_bwd_workspace_bytes", "owl_gemm_slab_workspace_bytes"):
+              "owl_attention_bwd_workspace_bytes", "owl_gemm_slab_workspace_bytes", "owl_gemm_nt_plan"):
         assert q in protos, q
 
 
@@ -66,6 +66,14 @@ def test_argument_validation_sets_error_without_gpu(built):
     with pytest.raises(_lib.OwlLibError, match="null pointer"):
         _lib.call("owl_gemm_nt_bf16", None, 0, None, 0, 0, None, 0, 0, None, None, 0, None, None, 0, 1, 4, 64, 1.0, 1, 0, 0)
     assert "null pointer" in _lib.last_error()
+    # the patch gathers (epilogues 7, 12) run through owl_patch_embed_bf16 only, whatever the shape: refused before any kernel is chosen (the pointers
+    # are host memory nothing reads)
+    import torch
+    h = torch.zeros(8)
+    for epi in (7, 12):
+        for (M, N, K) in ((128, 128, 64), (4096, 1024, 768)):
+            with pytest.raises(_lib.OwlLibError, match=f"unknown epilogue {epi}"):
+                _lib.call("owl_gemm_nt_bf16", None, epi, h, K, M, h, K, N, None, h, N, None, None, 0, M, N, K, 1.0, 1, 0, 0)
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

@@ -49,7 +49,7 @@ def test_constants_of_the_bounds():
 
 
 def test_shapes_reach_the_kernels_named():
-    """From the dispatcher's conditions (gemm.hip:362-423, restated in gemm_reference.dispatch_path): (2900, 1000, 128) is the smallest-M problem of 48
+    """From the planner's conditions (gemm_plan.h, gemm_plan, restated in gemm_reference.dispatch_path): (2900, 1000, 128) is the smallest-M problem of 48
     tiles -- tile 6 takes the half-height kernel on all of it, tile 0 the two-phase one; the tall case splits into one whole round on the two-phase
     kernel and 44 remainder tiles on the half-height one.  N = 248 (300 x 1 tiles as well) would NOT: the automatic rule wants N >= 256."""
     M, N, K = R.SHAPES[-1]

@@ -173,7 +173,10 @@ def _run_all_tiles(call, tiles, poison, where):
         d = max(float((results[128][k].double() - base[k].double()).abs().max()) for k in base)
         print(f"GEMMREF {where} form={call.form} tile128_vs_256 equal={_equal(results[128], base)} maxdiff={d:.3g}")
     for tile, worst in tally:
-        path = "+".join(k for k, _ in R.dispatch_path(call.epi, call.M, call.N, call.K, tile, call.a_rows)) if tile in R.TILES else "tuning"
+        lib_path = R.library_path(call.epi, call.M, call.N, call.K, tile, call.a_rows, splits=call.splits)          # what the library says it launched
+        if tile in R.TILES:
+            assert lib_path == R.dispatch_path(call.epi, call.M, call.N, call.K, tile, call.a_rows), (call.form, tile, lib_path)
+        path = "+".join(k for k, _ in lib_path)
         print(f"GEMMREF {where} epi={R.EPI_NAMES[call.epi]} form={call.form} tile={tile} path={path} " + " ".join(f"{k}={v:.3f}" for k, v in worst.items()))
     assert not fails, where + "\n" + "\n".join(fails)
 
@@ -223,8 +226,8 @@ TALL_FORMS = [("bias", "randn", (0, 7, 256)), ("qgelu", "tails", (0, 7, 256)), (
 @pytest.mark.parametrize("form,profile,tiles", TALL_FORMS, ids=[f[0] for f in TALL_FORMS])
 def test_gemm_tall_whole_round_plus_half_height_remainder(form, profile, tiles):
     """300 x 1 tiles of 256: tile 0 runs one whole round (M_main = 65 536 rows) on the two-phase kernel and the 44 remainder tiles on the half-height
-    kernel (gemm.hip:398-419; asserted with the arithmetic of _gemm_split); tile 7 the two-phase kernel alone (persistent: 300 items), tile 256 the
-    single-phase reference.  Rows sampled by the rule of _gemm_rows: every 128-row band, both sides of the split row, the first and last rows;
+    kernel (gemm_plan.h, gemm_plan; asserted with the arithmetic of gemm_split); tile 7 the two-phase kernel alone (persistent: 300 items), tile 256 the
+    single-phase reference.  Rows sampled by the rule of sample_rows: every 128-row band, both sides of the split row, the first and last rows;
     the bits of ALL rows are compared across the kernels."""
     M, N, K = R.TALL
     M_main = R.gemm_split(M, N, 0)

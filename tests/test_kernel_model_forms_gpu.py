@@ -13,9 +13,9 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from owl_vit_object_detection_amd import _lib, ops, rng  # noqa: E402
+from tests import gemm_reference  # noqa: E402
 
 DEV = "cuda"
-CHIP_CUS = 256
 
 
 def report(name, got, ref, atol, rtol):
@@ -301,29 +301,6 @@ def test_cast_f32_bf16_trip_loop(n):
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # 6. GEMM at model row counts
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def _gemm_split(M, N, tile):
-    """M_main of the automatic kernel choice (gemm.hip: whole rounds of 256 x 256 tiles + one round of 128 x 256 remainder tiles), or None."""
-    if tile != 0 or N > 1024:
-        return None
-    tm, tn = (M + 255) // 256, (N + 255) // 256
-    items = tm * tn
-    full_rounds = items // CHIP_CUS
-    tm_main = (full_rounds * CHIP_CUS) // tn
-    rem_tiles = (tm - tm_main) * tn
-    if full_rounds >= 1 and tm_main >= 1 and rem_tiles > 0 and 2 * rem_tiles <= CHIP_CUS and items - full_rounds * CHIP_CUS > 0:
-        return tm_main * 256
-    return None
-
-
-def _gemm_rows(M, M_main):
-    """Rows to check: the first tile, one row of every 128-row band (offset varying), both sides of M_main, the last rows."""
-    rows = {0, 1, 127, 128, 255, M - 1, M - 2, M - 129}
-    rows.update(b * 128 + (b * 37) % 128 for b in range((M + 127) // 128))
-    if M_main is not None:
-        rows.update({M_main - 256, M_main - 1, M_main, M_main + 1, M_main + 127, M_main + 128})
-    return torch.tensor(sorted(r for r in rows if 0 <= r < M), device=DEV)
-
-
 GEMM_SHAPES = [
     # B/16 batch 32 (M = 32 x 2312)
     ("b16_qkv", 73984, 2304, 768, ops.EPI_BIAS_BF16),
@@ -346,7 +323,7 @@ def test_gemm_model_row_counts(name, M, N, K, epi, tile):
     plus one round of half-height remainder tiles (gemm_pph.hip) from M_main on (asserted to happen); tile 7 the ping-pong kernel on the whole
     problem.  Sampled rows (first tile, every 128-row band, both sides of M_main, the last rows) against float64 A W^T + bias, then the epilogue
     (quick-GELU + its saved derivative quick_gelu'(u); the dX GEMM's product with a saved derivative); rows past M stay zero."""
-    M_main = _gemm_split(M, N, tile)
+    M_main = gemm_reference.gemm_split(M, N, tile)
     if name in ("b16_outproj", "b16_fc2") and tile == 0:
         assert M_main is not None and 0 < M_main < M, "the model's B/16 N = 768 GEMMs are expected to split into whole rounds + half-height tiles"
     seed = M + N + K + epi
@@ -366,7 +343,7 @@ def test_gemm_model_row_counts(name, M, N, K, epi, tile):
         aux[:M] = (s * (1.0 + 1.702 * uu * (1.0 - s))).bfloat16()          # a saved quick-GELU derivative
         del uu, s
     ops.gemm(epi, A, W, out, bias=None if epi == ops.EPI_DQGELU_BF16 else bias, aux=aux, M=M, tile=tile)
-    r = _gemm_rows(M, M_main)
+    r = torch.tensor(gemm_reference.sample_rows(M, M_main), device=DEV)
     acc = A[r].double() @ W.double().t()
     atol = K * 2.0 ** -20                                # f32 accumulation over K
     rtol = 2.0 ** -7                                     # two bf16 rounding steps (half an ulp each) at the worst place in a binade

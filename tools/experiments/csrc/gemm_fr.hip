@@ -5,7 +5,7 @@
 // intervals in which the CU's matrix pipe idles.  Here a CU hosts two workgroups that share nothing -- no LDS, no barrier -- so one's epilogue, tile
 // ramp and LOAD work run under the other's MFMAs with no code coupling them; each SIMD holds one wave of each.
 //   tile 128 x 256, four waves, wave wc = all 128 rows x the 64-column slice wc: acc[4][2] of 32 x 32 -- exactly one wave GROUP of gemm_pp2.hip, hence
-//   the same per-wave epilogue code (gemm_common.h) and, K-steps consumed in order on the same MFMA shape, the same bits as every other kernel here;
+//   the same per-wave epilogue code (gemm_plan.h) and, K-steps consumed in order on the same MFMA shape, the same bits as every other kernel here;
 //   BK = 32: a stage = A 128 x 32 (8 KiB) + B 256 x 32 (16 KiB); three stages + two bias slices = 74 KiB per workgroup, 148 of the CU's 160 KiB;
 //   LDS image: 64-byte rows, the four 16-byte chunks of a row XOR-swizzled with ((row >> 2) & 3) on the DMA source and on the fragment reads
 //   (conflict-free for ds_read_b128's lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31}: their row quads carry four different keys);
@@ -368,9 +368,10 @@ static int launch_fr(hipStream_t s, GemmP p) {
     return launch_fr_k<EPI, false>(s, p, nitems);
 }
 
-// called from gemm.hip's dispatcher; returns 1 if this variant does not handle `epi` (or the shape: K must hold at least three K-steps of 32)
+// called from gemm.hip for the steps gemm_plan gives this kernel; the cases are fr_takes (gemm_plan.h).  K must hold at least three K-steps of 32: the
+// planner sends nothing below K = 128
 int owl_gemm_fr_launch(hipStream_t s, int epi, const GemmP& p) {
-    if (p.K < 3 * FBK || p.K % FBK != 0) return 1;
+    OWL_CHECK_ARG(p.K >= 3 * FBK && p.K % FBK == 0, "owl_gemm_fr_launch: K = %lld (planner and launcher disagree)", (long long)p.K);
     switch (epi) {
         case EPI_BIAS_BF16: return launch_fr<EPI_BIAS_BF16>(s, p);
         case EPI_QGELU_BF16: return launch_fr<EPI_QGELU_BF16>(s, p);
@@ -379,7 +380,7 @@ int owl_gemm_fr_launch(hipStream_t s, int epi, const GemmP& p) {
         case EPI_DGELU_BF16: return launch_fr<EPI_DGELU_BF16>(s, p);
         case EPI_F32: return launch_fr<EPI_F32>(s, p);
         case EPI_ACC_F32: return launch_fr<EPI_ACC_F32>(s, p);
-        default: return 1;
+        default: owl_set_error("owl_gemm_fr_launch: epilogue %d is not one of fr_takes (planner and launcher disagree)", epi); return -1;
     }
 }
 #endif  // OWL_TUNING

@@ -358,7 +358,7 @@ static int launch_pp(hipStream_t s, GemmP p, int slots_override, int persistent_
     return 0;
 }
 
-// called from gemm.hip's dispatcher; returns 1 if this variant does not handle `epi`
+// called from gemm.hip for the steps gemm_plan gives this kernel; the cases are pp4_takes (gemm_plan.h)
 int owl_gemm_pp_launch(hipStream_t s, int epi, const GemmP& p, int slots_override, int persistent_on, int nostore) {
     switch (epi) {
         case EPI_BIAS_BF16:
@@ -379,7 +379,7 @@ int owl_gemm_pp_launch(hipStream_t s, int epi, const GemmP& p, int slots_overrid
         case EPI_DGELU_BF16: return launch_pp<EPI_DGELU_BF16>(s, p, slots_override, persistent_on, nostore);
         case EPI_F32: return launch_pp<EPI_F32>(s, p, slots_override, persistent_on, nostore);           // class head e = W feats + b, dfeats
         case EPI_ACC_F32: return launch_pp<EPI_ACC_F32>(s, p, slots_override, persistent_on, nostore);   // dfeats += (box head)
-        default: return 1;
+        default: owl_set_error("owl_gemm_pp_launch: epilogue %d is not one of pp4_takes (planner and launcher disagree)", epi); return -1;
     }
 }
 #endif  // OWL_TUNING (whole file)

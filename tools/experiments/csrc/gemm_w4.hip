@@ -216,12 +216,12 @@ static int launch_w4(hipStream_t s, GemmP p) {
     return 0;
 }
 
-// called from gemm.hip's dispatcher; returns 1 if this variant does not handle `epi`
+// called from gemm.hip for the steps gemm_plan gives this kernel; the cases are w4_takes (gemm_plan.h)
 int owl_gemm_w4_launch(hipStream_t s, int epi, const GemmP& p) {
     switch (epi) {
         case EPI_BIAS_BF16: return launch_w4<EPI_BIAS_BF16>(s, p);
         case EPI_QGELU_BF16: return launch_w4<EPI_QGELU_BF16>(s, p);
-        default: return 1;
+        default: owl_set_error("owl_gemm_w4_launch: epilogue %d is not one of w4_takes (planner and launcher disagree)", epi); return -1;
     }
 }
 
