@@ -32,7 +32,7 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's); still 8, additive again: + owl_gemm_nt_plan and the OWL_GEMM_KERNEL_* ids (which kernels a GEMM call launches; host query).  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's); still 8, additive again: + owl_gemm_nt_plan and the OWL_GEMM_KERNEL_* ids (which kernels a GEMM call launches; host query); still 8, additive again: + owl_prefix_emit, owl_prefix_gather (the frozen-prefix activation cache).  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
 #define OWL_ABI_VERSION 8
 const char* owl_last_error(void);
@@ -310,6 +310,20 @@ int owl_adamw_step(void* stream, float* p, const float* g, float* m, float* v, v
 int owl_grad_norm_workspace_bytes(int64_t n, int64_t* bytes);
 int owl_grad_sumsq(void* stream, const float* g, int64_t n, void* workspace);
 int owl_adamw_step_grouped(void* stream, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale, const int64_t* seg_end, const float* seg_lr, const float* seg_wd, int nseg, float max_norm, const void* workspace, float* norm_out);
+
+/* ---- frozen-prefix activation cache (still ABI 8: additive; prefix_cache.py, csrc/prefix_cache.hip) -------------------------------------------------------------
+ * Under a freeze rule the residual stream that the first non-frozen consumer normalises depends on the pixels alone: it is kept per image (f32 blocks of
+ * block_elems = Tp D elements) and the frozen layers below it are skipped for images already kept.
+ *   owl_prefix_emit    for each of n freshly computed images j: s = (xs[j] + delta1[j]) + delta2[j] -- block j of the COMPACTED operands xs (f32) and
+ *                      delta1 / delta2 (bf16, optional; delta2 only with delta1): the operands, the order and the plain f32 adds of owl_add_layernorm_fwd, so
+ *                      its no-delta form on s gives the bits of its delta form on the operands -- written to dst_addr[j] and, where slot_addr[j] != 0, to
+ *                      slot_addr[j] as well.  No destination may overlap xs (refused).
+ *   owl_prefix_gather  for each of n kept images j: the block at src_addr[j] is copied to dst_addr[j] (one source may serve several destinations).
+ * dst_addr / slot_addr / src_addr are HOST arrays of n DEVICE addresses, read by this call and passed to the kernels by value (no host-to-device copy,
+ * no sync); 64 images per launch, longer lists take several launches.  Every address and block 16-byte aligned: block_elems % 8 == 0.  No atomics, no
+ * scratch: pure streams.                                                                                                                            */
+int owl_prefix_emit(void* stream, const float* xs, const void* delta1_bf16, const void* delta2_bf16, int64_t n, int64_t block_elems, const int64_t* dst_addr, const int64_t* slot_addr);
+int owl_prefix_gather(void* stream, int64_t n, int64_t block_elems, const int64_t* src_addr, const int64_t* dst_addr);
 
 /* ---- utilities ------------------------------------------------------------------------------------ */
 int owl_cast_f32_bf16(void* stream, const float* in, void* out, int64_t n);

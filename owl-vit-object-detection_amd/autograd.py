@@ -53,10 +53,11 @@ def _attach_grads(model):
 
 class OwlViTFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, image, *params):
-        boxes, sims = model._forward_impl(image, save=True)
+    def forward(ctx, model, image, image_ids, *params):
+        """image_ids: None, or the checked id list of the frozen-prefix cache (models.OwlViT.forward); `image` may then be None."""
+        boxes, sims = model._forward_impl(image, save=True, ids=image_ids)
         ctx.model = model
-        ctx.B = image.shape[0]
+        ctx.B = image.shape[0] if image_ids is None else len(image_ids)
         ctx.sims = sims
         ctx.gen = model._workspace(ctx.B)["gen"]
         return boxes, sims
@@ -85,7 +86,7 @@ class OwlViTFunction(torch.autograd.Function):
             model._param_event = ev
         else:
             backward_impl(model, B, d_boxes, d_sims, ctx.sims)
-        return (None, None) + (None,) * len(model.flat_offsets)
+        return (None, None, None) + (None,) * len(model.flat_offsets)
 
 
 def _bws(model, B):

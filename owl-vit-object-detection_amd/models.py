@@ -23,6 +23,7 @@ import torch.nn as nn
 from . import _lib, ops, weights as W
 from .config import OwlConfig, check_image_size, get_config, table_grid
 from .postprocess import PostProcess  # noqa: F401  (the reference exports it from src/models.py:122)
+from .prefix_cache import PrefixCache, _id_list
 
 
 def box_bias_table(grid: int) -> torch.Tensor:
@@ -234,6 +235,11 @@ class OwlViT(nn.Module):
         # checkpointing while a deferred optimizer step (ddp.DataParallel(overlap=True)) is still running on its side stream: order the
         # current stream behind it before any parameter is read
         self.register_state_dict_pre_hook(lambda module, prefix, keep_vars: module._wait_params())
+        # Frozen-prefix activation cache (prefix_cache.py; off until enable_prefix_cache()): with `model(image, image_ids=ids)` the residual stream at the
+        # entry of the first non-frozen consumer is kept per id, and the frozen layers below it run on the images not yet kept only.  Whatever may change
+        # a frozen tensor empties it.
+        self.prefix_cache = None
+        self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate_prefix())
 
     # -- module-tree plumbing -----------------------------------------------------------------------
     def _attach(self, dotted: str, p: nn.Parameter):
@@ -428,6 +434,7 @@ class OwlViT(nn.Module):
     def _refresh_pos(self):
         """Run grid != native grid: the table the embeddings read follows the parameter (one launch; every forward with trainable embeddings calls it where
         the parameter is known to be current, i.e. behind _wait_params)."""
+        self._invalidate_prefix()          # (a frozen table re-made: what the kept states were computed from may have changed)
         if self._pos_used is not None:
             cfg = self.cfg
             ops.pos_resample(self._byname[_POS].detach(), self._pos_used, cfg.native_grid, cfg.grid, cfg.hidden)
@@ -440,7 +447,10 @@ class OwlViT(nn.Module):
         """bf16 copies of the trainable tensors: one cast over the flat bucket.  Every forward calls it, except the first forward after a
         fused AdamW step (whose kernel writes the copy itself and leaves a one-shot token, see __init__).  The only window left: a write
         that bypasses the version counter (`p.data.copy_()`, a raw-pointer kernel) BETWEEN FusedAdamW.step() and the next forward -- call
-        this method after such a write."""
+        this method after such a write.  force=True (a caller's own call, as opposed to a forward's) also empties the frozen-prefix activation cache:
+        the caller is telling the model that tensors were written behind its back."""
+        if force:
+            self._invalidate_prefix()
         ops.cast_bf16(self.flat_param, self.flat_bf16)
         self._bf16_current = False
         self._refresh_patch_weight()
@@ -454,6 +464,7 @@ class OwlViT(nn.Module):
         """`.to()` / `.cuda()` / `.half()` / `.float()` / `.cpu()` replace every `param.data`, which would silently detach the 29 trainable
         tensors from the flat parameter / gradient / bf16 buckets the kernels read.  The model is built on its device in f32 (the reference's
         `.to(device)`, src/models.py:191, is done by construction): a call that changes nothing is accepted, anything else raises."""
+        self._invalidate_prefix()
         probe = torch.empty(0, dtype=torch.float32, device=self.device_)
         out = fn(probe)
         if out.dtype != probe.dtype or out.device != probe.device:
@@ -461,6 +472,44 @@ class OwlViT(nn.Module):
                 f"OwlViT lives on {self.device_} in float32 (trainable tensors are views of one flat bucket; compute is bf16 inside the kernels): "
                 f"moving / casting the module to {out.device} / {out.dtype} is not supported -- build it with load_model(labelmap, device)")
         return self
+
+    # -- frozen-prefix activation cache ---------------------------------------------------------------------
+    def enable_prefix_cache(self, max_bytes=None, max_images=None):
+        """Switch the frozen-prefix activation cache on (prefix_cache.PrefixCache; max_bytes None = its DEFAULT_MAX_BYTES; slabs are allocated as they
+        fill).  From then on `model(image, image_ids=ids)` keeps, per id, the f32 residual stream the first non-frozen consumer normalises -- the first
+        LayerNorm of the lowest encoder layer the backward crosses, or the final LayerNorms under a heads-only set -- and skips the patch embedding,
+        pre_layernorm and the encoder layers below it for ids already kept.  Same bits as without it.  An id must identify the PIXELS the model is
+        handed: never pass ids together with a random augmentation.  Needs a frozen prefix: raises ValueError where layer 0, pre_layernorm or the
+        embeddings train."""
+        if self._chain_low == 0:
+            keep = W.FREEZE_KEEP if self._keep is None else self._keep
+            raise ValueError(f"enable_prefix_cache: the trainable set {tuple(keep)!r} leaves no frozen prefix (the backward reaches "
+                             f"{self.backward_floor if not isinstance(self.backward_floor, int) else 'encoder layer 0'}): nothing below the first trainable tensor is constant")
+        self.prefix_cache = PrefixCache(self.cfg.tokens_padded * self.cfg.hidden, max_bytes, max_images, self.device_, key=self.cfg)
+        return self.prefix_cache
+
+    def disable_prefix_cache(self):
+        """Drop the cache and its slabs; `image_ids=` is refused again."""
+        self.prefix_cache = None
+
+    def _invalidate_prefix(self):
+        if getattr(self, "prefix_cache", None) is not None:
+            self.prefix_cache.clear()
+
+    @staticmethod
+    def _take_images(image, pos):
+        """image[pos] for ascending positions, without an index tensor (which would be a host-to-device copy): the batch itself, or one concatenation of
+        its runs."""
+        if pos == list(range(image.shape[0])):
+            return image
+        runs, a = [], 0
+        while a < len(pos):
+            b = a
+            while b + 1 < len(pos) and pos[b + 1] == pos[b] + 1:
+                b += 1
+            runs.append(image[pos[a]:pos[b] + 1])
+            a = b + 1
+        return runs[0] if len(runs) == 1 else torch.cat(runs)
 
     @property
     def _tail_stream(self):
@@ -554,7 +603,7 @@ class OwlViT(nn.Module):
         # delta through the fast wide-store epilogue, and LN does x += delta while it normalises.
         x_cur = R(Ls["x_in"]) if sv else xs
         if pending is None:
-            if sv:
+            if sv and x_cur.data_ptr() != xs.data_ptr():          # (the frozen-prefix cache hands the kept sum over in x_in itself)
                 x_cur.copy_(xs)
             ops.layernorm(x_cur, lw["g1"], lw["be1"], h, M, D, st1, cfg.ln_eps)
         else:
@@ -586,12 +635,25 @@ class OwlViT(nn.Module):
         st["pending1"] = d1 if defer else None
 
     # -- forward ---------------------------------------------------------------------------------------
-    def _forward_impl(self, image: torch.Tensor, save: bool):
+    def _forward_impl(self, image: torch.Tensor, save: bool, ids=None):
+        """ids (list of B ints, forward() has checked them; None = no cache): the frozen-prefix cache's path -- the input stage and the encoder layers below
+        the boundary run on the images not yet kept, compacted to the first rows of the same workspace, then the kept and the fresh states meet in the
+        boundary buffer and the rest runs on the whole batch as ever."""
         cfg = self.cfg
         D, I, H, Tp, T, P, Dt, C = cfg.hidden, cfg.mlp, cfg.heads, cfg.tokens_padded, cfg.tokens, cfg.patches, cfg.text_dim, cfg.n_classes
-        B = image.shape[0]
-        if tuple(image.shape[1:]) != (3, cfg.image_size, cfg.image_size):
+        B = image.shape[0] if ids is None else len(ids)
+        if image is not None and tuple(image.shape[1:]) != (3, cfg.image_size, cfg.image_size):
             raise ValueError(f"image must be [B,3,{cfg.image_size},{cfg.image_size}], got {tuple(image.shape)}")
+        plan = None
+        if ids is not None:
+            cache = self.prefix_cache
+            if cache.key != cfg:          # kept states belong to one size and architecture
+                cache.clear()
+                cache.key = cfg
+            plan = cache.plan(ids)
+            if image is None and plan.miss_ids:
+                raise ValueError(f"image=None needs every id in the prefix cache; not kept: {plan.miss_ids}")
+        Bp = B if plan is None else len(plan.miss_pos)          # images the input stage and the frozen prefix run on
         ws = self._workspace(B, train=save)
         # model-global, monotonically increasing: a workspace rebuilt after an LRU eviction can never carry a generation an older autograd
         # node still holds (a per-workspace counter restarted at 0 and could collide: fwd(A) -> two other sizes evict A -> fwd(A) again)
@@ -605,7 +667,7 @@ class OwlViT(nn.Module):
         else:
             from_optimizer = False
             self._wait_params()
-            self.refresh_compute_weights()
+            self.refresh_compute_weights(force=False)
         if self._train_emb or self._train_pre:
             # the first trainable tensor is read by the embeddings (and a deferred tail's backward may still be reading the kept bf16 image): nothing of this
             # forward runs under a deferred tail
@@ -615,7 +677,11 @@ class OwlViT(nn.Module):
             if self._train_emb:
                 self._refresh_pos()                 # behind the wait above: the deferred tail's AdamW has written the table this reads
 
-        if image.dtype == torch.float32:
+        if plan is not None and 0 < Bp < B:
+            image = self._take_images(image, plan.miss_pos)
+        if Bp == 0:
+            img = None          # every image's boundary state is kept: none of the input stage runs
+        elif image.dtype == torch.float32:
             ops.cast_bf16(image.contiguous(), ws["img"])
             img = ws["img"]
         elif image.dtype == torch.bfloat16:
@@ -626,7 +692,9 @@ class OwlViT(nn.Module):
         x = ws["x"]
         pos = self._pos_table()
         low = save and self.backward_floor in ("pre_layernorm", "embeddings")
-        if low:
+        if Bp == 0:
+            pass
+        elif low:
             # the backward goes below layer 0: keep pre_layernorm's input and row statistics (and, for the patch-embedding weight gradient, the bf16 image)
             pw = self._pre_ws(B)
             if self._train_emb and img is not ws["img"]:
@@ -637,10 +705,10 @@ class OwlViT(nn.Module):
             ops.cls_rows(x_emb, P_["backbone.embeddings.class_embedding"], pos, B, Tp, D)
             ops.layernorm(x_emb, P_["backbone.pre_layernorm.weight"], P_["backbone.pre_layernorm.bias"], x, M, D, pw["st_pre"], cfg.ln_eps)
         else:
-            ops.patch_embed(img, self._fz["w_pe"], pos, x, B, cfg.image_size,
-                            cfg.patch_size, D, Tp, scratch=self._patch_scratch(B))
-            ops.cls_rows(x, P_["backbone.embeddings.class_embedding"], pos, B, Tp, D)
-            ops.layernorm(x, P_["backbone.pre_layernorm.weight"], P_["backbone.pre_layernorm.bias"], x, M, D, eps=cfg.ln_eps)
+            ops.patch_embed(img, self._fz["w_pe"], pos, x, Bp, cfg.image_size,
+                            cfg.patch_size, D, Tp, scratch=self._patch_scratch(Bp))
+            ops.cls_rows(x, P_["backbone.embeddings.class_embedding"], pos, Bp, Tp, D)
+            ops.layernorm(x, P_["backbone.pre_layernorm.weight"], P_["backbone.pre_layernorm.bias"], x, Bp * Tp, D, eps=cfg.ln_eps)
 
         # ---- encoder.  No kernel of it couples images, so the batch is run as `encoder_streams` sub-batches (contiguous row ranges of the
         #      same buffers), each on its own HIP stream, layer by layer: the idle CUs of one sub-batch's last GEMM round / attention tail
@@ -651,40 +719,79 @@ class OwlViT(nn.Module):
         # streams wait for a deferred tail.  None: no encoder layer does; the wait then sits in front of the final LayerNorms.
         tl = self._chain_low
         param_event, self._param_event = self._param_event, None
-        chunks = self._encoder_chunks(B)
         main = torch.cuda.current_stream()
         if save and tl is not None:        # first use allocates (and zero-fills, on THIS stream) the kept activations: before any other stream may write them
             for i in range(tl, cfg.layers):
                 self._layer_ws(B, i)
-        if len(chunks) > 1:
-            if self._fork_ev is None:
-                self._fork_ev = torch.cuda.Event()
-            self._fork_ev.record(main)
-        states = []
-        for c, (b0, nb) in enumerate(chunks):
-            st = dict(b0=b0, nb=nb, stream=main if c == 0 else self._side_stream(c), xs=x[b0 * Tp:(b0 + nb) * Tp], pending=None, pending1=None, conc=len(chunks))
-            if c > 0:
-                st["stream"].wait_event(self._fork_ev)
-            states.append(st)
-        for i in range(cfg.layers):
-            for st in states:
-                with torch.cuda.stream(st["stream"]):
-                    if i == tl and param_event is not None:
-                        st["stream"].wait_event(param_event)    # everything above ran on frozen weights only (ddp overlap schedule)
-                    if i == tl and save and self.pretranspose and st is states[0]:
-                        self._pretranspose_weights()            # the backward's W^T copies, beside the rest of this forward and the loss chain
-                    self._encoder_layer(i, ws, B, save, st)
-        for c, st in enumerate(states):
-            if c > 0:
-                self._join[c].record(st["stream"])
-                main.wait_event(self._join[c])
-        # the sub-batches' residual streams / deferred MLP-branch outputs are row ranges of ONE buffer each: the merge kernel takes the batch
-        if tl is None and param_event is not None:
-            main.wait_event(param_event)            # heads-only sets: the whole encoder ran on frozen weights
+
+        def run_layers(lo, hi, nb_all, buf):
+            """Layers [lo, hi) on images [0, nb_all), whose residual stream enters in `buf`, as sub-batches on their streams; joined on `main`."""
+            nonlocal param_event
+            chunks = self._encoder_chunks(nb_all)
+            if len(chunks) > 1:
+                if self._fork_ev is None:
+                    self._fork_ev = torch.cuda.Event()
+                self._fork_ev.record(main)
+            states = []
+            for c, (b0, nb) in enumerate(chunks):
+                st = dict(b0=b0, nb=nb, stream=main if c == 0 else self._side_stream(c), xs=buf[b0 * Tp:(b0 + nb) * Tp], pending=None, pending1=None, conc=len(chunks))
+                if c > 0:
+                    st["stream"].wait_event(self._fork_ev)
+                states.append(st)
+            for i in range(lo, hi):
+                for st in states:
+                    with torch.cuda.stream(st["stream"]):
+                        if i == tl and param_event is not None:
+                            st["stream"].wait_event(param_event)    # everything above ran on frozen weights only (ddp overlap schedule)
+                        if i == tl and save and self.pretranspose and st is states[0]:
+                            self._pretranspose_weights()            # the backward's W^T copies, beside the rest of this forward and the loss chain
+                        self._encoder_layer(i, ws, B, save, st)
+            for c, st in enumerate(states):
+                if c > 0:
+                    self._join[c].record(st["stream"])
+                    main.wait_event(self._join[c])
+            return states
+
         last = cfg.layers - 1
-        xs = self._layer_ws(B, last)["x_mid"] if (save and tl is not None) else x
+        chunks = self._encoder_chunks(B)          # (the whole batch's: what the heads' fork below goes by)
+        if plan is None:
+            states = run_layers(0, cfg.layers, B, x)
+            # the sub-batches' residual streams / deferred MLP-branch outputs are row ranges of ONE buffer each: the merge kernel takes the batch
+            if tl is None and param_event is not None:
+                main.wait_event(param_event)            # heads-only sets: the whole encoder ran on frozen weights
+            xs = self._layer_ws(B, last)["x_mid"] if (save and tl is not None) else x
+            pending = ws["d2"]
+        else:
+            # ---- frozen-prefix cache: layers below the boundary on the compacted misses (rows [0, Bp Tp) of the same buffers); then, on the main stream, the
+            #      fresh sums go to their positions and slots and the kept ones are copied in; layers from the boundary up on the whole batch.  The boundary
+            #      buffer is what the first non-frozen consumer reads anyway where the backward keeps it (x_in of layer tl; x_fin under a heads-only set) and
+            #      a buffer of the workspace's own otherwise -- never `x`, which holds the compacted source.
+            first = cfg.layers if tl is None else tl
+            pre = run_layers(0, first, Bp, x) if Bp else []
+            if param_event is not None:
+                # the boundary buffer and everything above are what a deferred tail's backward may still be reading; the streams of the second leg fork
+                # from this one behind the wait
+                main.wait_event(param_event)
+                param_event = None
+            if save:
+                bound = self._layer_ws(B, tl)["x_in"] if tl is not None else ws["x_fin"]
+            else:
+                if "x_pc" not in ws:
+                    ws["x_pc"] = ops.zeros_rows(M, D, torch.float32, self.device_)
+                bound = ws["x_pc"]
+            if pre:
+                assert all(st["xs"].data_ptr() == x.data_ptr() + st["b0"] * Tp * D * 4 and st["pending"] is not None for st in pre)
+                d1 = ws["d1"] if pre[0]["pending1"] is not None else None          # (xs + d1) + d2: the operands and order of the LayerNorm that would have read them
+                deltas = (d1, ws["d2"]) if d1 is not None else (ws["d2"], None)
+                cache.fill(plan, bound, x, *deltas)
+            else:
+                cache.fill(plan, bound)
+            states = run_layers(first, cfg.layers, B, bound)
+            if tl is None:
+                xs, pending = bound, None          # the kept sum IS the final residual stream: the merge kernel's no-delta form (the backward reads it where it lies)
+            else:
+                xs, pending = (self._layer_ws(B, last)["x_mid"] if save else bound), ws["d2"]
         assert all(st["xs"].data_ptr() == xs.data_ptr() + st["b0"] * Tp * D * 4 for st in states)
-        pending = ws["d2"]
 
         # ---- final residual add + post_layernorm (all tokens) * class token -> post_post_layernorm
         #      (ref src/models.py:80-86); the final residual stream is materialised in `x` for the backward
@@ -723,16 +830,30 @@ class OwlViT(nn.Module):
             main.wait_event(self._join[1])
         return pred_boxes, pred_sims
 
-    def forward(self, image: torch.Tensor):
-        """ref src/models.py:98-119: returns (pred_boxes xyxy, None, pred_sims, None)."""
+    def forward(self, image: torch.Tensor, image_ids=None):
+        """ref src/models.py:98-119: returns (pred_boxes xyxy, None, pred_sims, None).
+
+        image_ids (None = no cache, today's path): B integers (a sequence or a CPU tensor; a device tensor is refused: reading it would be a sync) that
+        identify the pixels of each image, e.g. the dataset index -- see enable_prefix_cache().  `image` may be None when every id is kept."""
+        ids = None
+        if image_ids is not None:
+            if self.prefix_cache is None:
+                raise RuntimeError("image_ids= needs the frozen-prefix cache: call model.enable_prefix_cache() first")
+            ids = _id_list(image_ids)
+            if image is not None and image.shape[0] != len(ids):
+                raise ValueError(f"image_ids has {len(ids)} entries for a batch of {image.shape[0]} images")
+            if not ids:
+                raise ValueError("image_ids is empty")
+        elif image is None:
+            raise ValueError("image=None needs image_ids= (and every id kept by the prefix cache)")
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if need_grad:
             self._check_trainable_set()
             from .autograd import OwlViTFunction
             names = list(self.flat_offsets.keys())
-            boxes, sims = OwlViTFunction.apply(self, image, *[self._byname[n] for n in names])
+            boxes, sims = OwlViTFunction.apply(self, image, ids, *[self._byname[n] for n in names])
         else:
-            boxes, sims = self._forward_impl(image, save=False)
+            boxes, sims = self._forward_impl(image, save=False, ids=ids)
         return (boxes, None, sims, None)
 
 

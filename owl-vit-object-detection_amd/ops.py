@@ -195,6 +195,33 @@ def transpose_bf16(src, dst, R, C, ld_in=None, ld_out=None):
     return dst
 
 
+# ---- frozen-prefix activation cache (csrc/prefix_cache.hip) -------------------------------------------------
+def _addr_table(addrs):
+    """Host int64 array of device addresses (the library reads it during the call and hands it to the kernel by value: no device copy)."""
+    return torch.tensor([int(a) for a in addrs], dtype=torch.int64)
+
+
+def prefix_emit(xs, delta1, delta2, n, block_elems, dst_addr, slot_addr):
+    """For each of the n images of the compacted batch: s = (xs[j] + delta1[j]) + delta2[j] (deltas bf16, optional) -> the f32 block at device address
+    dst_addr[j] and, where slot_addr[j] != 0, at slot_addr[j].  dst_addr / slot_addr: sequences of n ints."""
+    _chk(xs, torch.float32, "xs"); _chk(delta1, torch.bfloat16, "delta1"); _chk(delta2, torch.bfloat16, "delta2")
+    n, block_elems = int(n), int(block_elems)
+    if len(dst_addr) != n or len(slot_addr) != n:
+        raise ValueError(f"prefix_emit: dst_addr / slot_addr must have n = {n} entries")
+    for t, name in ((xs, "xs"), (delta1, "delta1"), (delta2, "delta2")):
+        if t is not None and t.numel() < n * block_elems:
+            raise ValueError(f"prefix_emit: {name} must hold n blocks of {block_elems} elements")
+    _lib.call("owl_prefix_emit", stream(), xs, delta1, delta2, n, block_elems, _addr_table(dst_addr), _addr_table(slot_addr))
+
+
+def prefix_gather(n, block_elems, src_addr, dst_addr):
+    """For each of n images: the f32 block at device address src_addr[j] -> the block at dst_addr[j].  Sequences of n ints."""
+    n = int(n)
+    if len(src_addr) != n or len(dst_addr) != n:
+        raise ValueError(f"prefix_gather: src_addr / dst_addr must have n = {n} entries")
+    _lib.call("owl_prefix_gather", stream(), n, int(block_elems), _addr_table(src_addr), _addr_table(dst_addr))
+
+
 # ---- backward-side wrappers ---------------------------------------------------------------------------
 _partials = {}
 
