@@ -5,9 +5,11 @@
 // and their dX / dW backward forms).
 //
 // CDNA4 structure (template <EPI, BM, BN, WM, WN>):
-//   * block tile BM x BN x 64, (BM/WM) x (BN/WN) waves, each wave a WM x WN sub-tile of
-//     v_mfma_f32_32x32x16_bf16 accumulators.  Two instantiations: 256x256 with 8 waves of 128x64
-//     (the workhorse: one K-step is 32 MFMAs per wave, long enough to cover the next tile's load
+//   * block tile BM x BN x 64, (BM/WM) x (BN/WN) waves, each wave a WM x WN sub-tile of 32 x 32 accumulator
+//     blocks, each block four v_mfma_f32_16x16x32_bf16 accumulators (gemm_common.h, AccBlock: the shape on which
+//     the chip holds the higher clock, profiles/mfma_shape.md; the epilogues get the 32x32x16 register layout).
+//     Two instantiations: 256x256 with 8 waves of 128x64
+//     (the workhorse: one K-step is 64 MFMAs per wave, long enough to cover the next tile's load
 //     latency, and 25 % less LDS traffic per FLOP) and 128x128 with 4 waves of 64x64 (small / thin shapes);
 //   * operand tiles go HBM -> LDS by direct LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave-instruction),
 //     double-buffered, ONE barrier per K-step (preceded by vmcnt(0) AND lgkmcnt(0): LDS reads must have returned,
@@ -48,7 +50,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_nt_kernel(Gem
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int hi = lane >> 5;
     const int nk_all = (int)(p.K / BK);
 
     // ---- work items = (tile, K-split); persistent: this workgroup walks items item, item+step, ... of
@@ -143,17 +144,9 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_nt_kernel(Gem
 
     const int wr = w / NWN, wc = w - wr * NWN;
     const int wr_ = wr, wc_ = wc;
-    int a_off[TI], a_sw[TI], b_off[TJ], b_sw[TJ];
-#pragma unroll
-    for (int i = 0; i < TI; i++) {
-        const int ra = wr * WM + i * 32 + (lane & 31);
-        a_off[i] = ra * 128; a_sw[i] = (ra >> 1) & 7;
-    }
-#pragma unroll
-    for (int j = 0; j < TJ; j++) {
-        const int rb = wc * WN + j * 32 + (lane & 31);
-        b_off[j] = A_BYTES + rb * 128; b_sw[j] = (rb >> 1) & 7;
-    }
+    // fragment offsets of k-step 0 (gemm_common.h, frag_off).  Swapped operands (every epilogue but the transposing one): the W rows are the MFMAs' row
+    // side, D rows = n, cols = m -> each lane owns 4 consecutive n of one m; TRANS: the A rows are.
+    const int a_frag_off = frag_off<TRANS>(wr * WM, lane), b_frag_off = A_BYTES + frag_off<!TRANS>(wc * WN, lane);
 
     // bf16-output epilogues on the 256-wide tile use the register path: element-wise math, pack, v_permlane32_swap
     // pairing -> 16-byte stores.  On gfx950 vmcnt counts stores too and is in-order, so the vmcnt(0) of the next K-step
@@ -173,13 +166,11 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_nt_kernel(Gem
     asm volatile("" ::: "memory");
     int cur = 0;
     while (true) {
-        f32x16 acc[TI][TJ];
+        AccBlock blk[TI][TJ];                         // 16x16x32 accumulators inside the K loop (gemm_common.h)
 #pragma unroll
         for (int i = 0; i < TI; i++)
 #pragma unroll
-            for (int j = 0; j < TJ; j++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+            for (int j = 0; j < TJ; j++) acc_block_zero(blk[i][j]);
         const int64_t cm0 = m0, cn0 = n0;
         const int csplit = split, ckt0 = kt0, ckt1 = kt1;
         const int next = item + item_step;
@@ -196,32 +187,32 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_nt_kernel(Gem
                 stage_bias(tile_parity ^ 1);
             }
             const unsigned char* tb = lds + cur * STAGE;
-            // software-pipelined fragments: the six ds_read_b128 of K-chunk kc+1 are issued BEFORE the eight MFMAs of
-            // chunk kc (sched_barrier pins the order; the compiler's own lgkmcnt(N) then waits only for the older set),
-            // so a wave covers its LDS latency with its own matrix work instead of stalling every two MFMAs.
-            bf16x8 fa[2][TI], fb[2][TJ];
-            auto rd = [&](int set, int kc) {
-                const int ch = kc * 2 + hi;
+            // software-pipelined fragments.  A stage is one k-step s of one 32-row A block i: TJ blocks = 4 TJ MFMAs.  The W fragments of the whole K-tile
+            // are read up front (k-step 0 first); the two A fragments of stage st + 1 are issued BEFORE the MFMAs of stage st (sched_barrier pins the
+            // order; the compiler's own lgkmcnt(N) then waits only for the older set), so a wave covers its LDS latency with its own matrix work.
+            // k-step outer: every accumulator sees k-step 0, then 1.
+            bf16x8 fb[TJ][4], fa[2][2];               // [j][2 s + half], [set][half]
+            auto rd_b = [&](int s) {
 #pragma unroll
-                for (int j = 0; j < TJ; j++) fb[set][j] = *(const bf16x8*)(tb + b_off[j] + ((ch ^ b_sw[j]) << 4));
+                for (int j = 0; j < TJ; j++)
 #pragma unroll
-                for (int i = 0; i < TI; i++) fa[set][i] = *(const bf16x8*)(tb + a_off[i] + ((ch ^ a_sw[i]) << 4));
+                    for (int h = 0; h < 2; h++) fb[j][2 * s + h] = frag_read(tb + j * 4096, b_frag_off, s, h);
             };
-            rd(0, 0);
+            auto rd_a = [&](int set, int st) {
 #pragma unroll
-            for (int kc = 0; kc < 4; kc++) {
-                const int cs = kc & 1;
-                if (kc < 3) rd(cs ^ 1, kc + 1);
+                for (int h = 0; h < 2; h++) fa[set][h] = frag_read(tb + (st % TI) * 4096, a_frag_off, st / TI, h);
+            };
+            rd_b(0); rd_a(0, 0); rd_b(1);
+#pragma unroll
+            for (int st = 0; st < 2 * TI; st++) {
+                const int cs = st & 1, s = st / TI, i = st % TI;
+                if (st + 1 < 2 * TI) rd_a(cs ^ 1, st + 1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int i = 0; i < TI; i++)
-#pragma unroll
-                    for (int j = 0; j < TJ; j++) {
-                        if constexpr (TRANS)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cs][i], fb[cs][j], acc[i][j], 0, 0, 0);
-                        else  // swapped: D rows = n, cols = m -> each lane owns 4 consecutive n of one m
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[cs][j], fa[cs][i], acc[i][j], 0, 0, 0);
-                    }
+                for (int j = 0; j < TJ; j++) {
+                    if constexpr (TRANS) mma_block_frags(blk[i][j], fa[cs][0], fa[cs][1], fb[j][2 * s], fb[j][2 * s + 1]);
+                    else mma_block_frags(blk[i][j], fb[j][2 * s], fb[j][2 * s + 1], fa[cs][0], fa[cs][1]);
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -229,6 +220,11 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_nt_kernel(Gem
             asm volatile("" ::: "memory");
             cur ^= 1;
         }
+        f32x16 acc[TI][TJ];                           // the blocks in the 32x32x16 accumulator layout the epilogues take
+#pragma unroll
+        for (int i = 0; i < TI; i++)
+#pragma unroll
+            for (int j = 0; j < TJ; j++) acc[i][j] = acc_block_32x32(blk[i][j]);
         if constexpr (WIDE) {
             const bool inner = (cm0 + BM <= p.M) && (cn0 + BN <= p.N);   // wave-uniform: no per-lane guards needed
             const float* lbias = (const float*)(lds + 2 * STAGE + tile_parity * (BN * 4)) + wc * WN;

@@ -64,6 +64,79 @@ __device__ __forceinline__ int xcd_remap(int bid, int ntile) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
+// ---- the MFMA block primitive of the family: one 32 x 32 accumulator block over one 64-wide K-tile as v_mfma_f32_16x16x32_bf16 -------------------------
+// The block is four 16 x 16 tiles t[a][b] (a: 16 rows of the MFMA's row-side operand, b: 16 columns of its column-side operand) and a K-tile two k-steps
+// of 32: 8 instructions of 16 cycles where v_mfma_f32_32x32x16_bf16 took 4 of 32; every accumulator sees k-step 0, then 1, K-tile after K-tile.
+// Operand layout of the instruction (lane = 16 g + c): row-side lane = row c, k = 8 g .. 8 g + 7 of the k-step; column-side lane = column c, same k;
+// result register r of lane (g, c) = row 4 g + r, column c.
+//
+// Fragments come from the family's LDS image ([rows][64 k] bf16, 128-byte rows, 16-byte chunk index XOR (row >> 1) & 7): k-step s, lane group g = chunk
+// 4 s + g.  The column side reads block rows 16 b + c.  The ROW side reads block row  16 a + frag_row_perm(c)  (bits 2 and 3 of c exchanged), so that
+// result register r of lane (g, c) in t[a][b] is block row  r + 4 (g >> 1) + 8 (2 a + (g & 1)),  column 16 b + c.  acc_block_32x32 then only has to
+// exchange t[a][1] of the lanes with g even against t[a][0] of the lanes with g odd (lanes l and l ^ 16: one v_permlane16_swap per register) to arrive at
+// the register layout of a v_mfma_f32_32x32x16_bf16 accumulator -- column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) -- which every
+// epilogue below takes.  Both reads are conflict-free under the image's XOR key: a ds_read_b128 lane group is four lanes of one g on rows {0-3, 12-15}
+// or {4-11} of the sixteen, keys {0, 1, 6, 7} or {2 .. 5}, and the row permutation maps each of the two row sets onto itself.
+struct AccBlock { f32x4 t[2][2]; };
+
+__device__ __forceinline__ void acc_block_zero(AccBlock& c) {
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) c.t[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+
+__device__ __forceinline__ int frag_row_perm(int c) { return (c & 3) | ((c & 8) >> 1) | ((c & 4) << 1); }
+
+// Byte offset of a lane's fragment of k-step 0 inside an image whose 32-row block starts at row `row0` (a multiple of 16); k-step 1 is the same offset
+// XOR 64 (frag_read), the second 16 rows + 2048, the next 32-row block + 4096.  ROW_SIDE: the row-side operand's permuted rows.
+template <bool ROW_SIDE>
+__device__ __forceinline__ int frag_off(int row0, int lane) {
+    const int c = lane & 15, r = ROW_SIDE ? frag_row_perm(c) : c;
+    return (row0 + r) * 128 + (((lane >> 4) ^ ((r >> 1) & 7)) << 4);
+}
+
+// fragment [2 s + h]: k-step s, 16-row half h of the block at byte offset `off` (frag_off) of the image `tile` (128-byte aligned)
+__device__ __forceinline__ bf16x8 frag_read(const unsigned char* tile, int off, int s, int h) {
+    return *(const bf16x8*)(tile + (off ^ (s << 6)) + h * 2048);
+}
+
+// one k-step of the block from its four fragments: r0 / r1 = the row side's two 16-row halves, c0 / c1 = the column side's
+__device__ __forceinline__ void mma_block_frags(AccBlock& c, const bf16x8& r0, const bf16x8& r1, const bf16x8& c0, const bf16x8& c1) {
+    c.t[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(r0, c0, c.t[0][0], 0, 0, 0);
+    c.t[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(r0, c1, c.t[0][1], 0, 0, 0);
+    c.t[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(r1, c0, c.t[1][0], 0, 0, 0);
+    c.t[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(r1, c1, c.t[1][1], 0, 0, 0);
+}
+
+// ... with fr / fc = the row-side / column-side fragments [2 s + half] of the whole K-tile
+__device__ __forceinline__ void mma_block_step(AccBlock& c, const bf16x8 (&fr)[4], const bf16x8 (&fc)[4], int s) {
+    mma_block_frags(c, fr[2 * s], fr[2 * s + 1], fc[2 * s], fc[2 * s + 1]);
+}
+
+// the whole K-tile: what one chain of four v_mfma_f32_32x32x16_bf16 (kc = 0..3) did
+__device__ __forceinline__ void mma_block(AccBlock& c, const bf16x8 (&fr)[4], const bf16x8 (&fc)[4]) {
+    mma_block_step(c, fr, fc, 0);
+    mma_block_step(c, fr, fc, 1);
+}
+
+// once per output tile, after the K loop: the block in the register layout of a 32x32x16 accumulator.
+// v_permlane16_swap(x, y): the odd 16-lane rows of x <-> the even rows of y.  With x = t[a][0], y = t[a][1]: afterwards x holds, in every lane, block rows
+// r + 4 hi + 8 (2 a) of column lane & 31 (even g: its own; odd g: the partner's t[a][1], columns 16 + c) and y block rows r + 4 hi + 8 (2 a + 1).
+__device__ __forceinline__ f32x16 acc_block_32x32(const AccBlock& c) {
+    f32x16 o;
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const float x = c.t[a][0][r], y = c.t[a][1][r];          // (by value: a bit cast straight from a vector element reads element 0)
+            const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
+            o[8 * a + r] = __uint_as_float(sw[0]);
+            o[8 * a + 4 + r] = __uint_as_float(sw[1]);
+        }
+    return o;
+}
+
 // ---- element-wise epilogue of ONE (row, 4 consecutive columns) quad -----------------------------------
 // v[4] = raw accumulators of output row `orow` (store row, already remapped for PATCH) at columns n..n+3.
 template <int EPI>

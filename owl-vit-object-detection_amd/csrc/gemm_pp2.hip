@@ -3,7 +3,10 @@
 //
 // gemm_pp.hip runs a K-tile as FOUR quadrant phases of 8 MFMAs on TWO accumulator tiles: two dependent chains, which one wave issues at
 // ~36 cycles per MFMA instead of 32 (a chain's next MFMA needs the previous one's result: `s_memtime` traces, tools/probe), and eight
-// barriers per K-tile.  Here a K-tile is TWO phases of 16 MFMAs on FOUR accumulator tiles (four independent chains, four deep):
+// barriers per K-tile.  Here a K-tile is TWO phases on FOUR accumulator tiles (four independent chains, four deep, when the tiles were single
+// v_mfma_f32_32x32x16_bf16 accumulators: 16 MFMAs per phase; now every 32 x 32 tile is a block of four v_mfma_f32_16x16x32_bf16 accumulators --
+// gemm_common.h, AccBlock -- and a phase 32 MFMAs of half the cycles: same tiles, fragments, waits and barriers, and the same bits, since the
+// two shapes round alike, tools/probe/mfma_shape_bits.hip; the chip holds a higher clock on this shape, profiles/mfma_shape.md):
 //     phase A: rows i0,i1 x columns j0,j1     LOAD A: A(i0,i1) + B(j0) + B(j1) fragments (16 ds_read_b128) + this wave's 4 A pieces
 //     phase B: rows i2,i3 x columns j0,j1     LOAD B: A(i2,i3) fragments (8; B stays in registers)           + this wave's 4 B pieces
 // The two groups (waves 0-3 / 4-7 = output rows 0-127 / 128-255, one wave of each per SIMD) run one barrier apart, as there.
@@ -190,9 +193,8 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(GemmP p) {
         return n_ops;
     };
 
-    const int a_row0 = grp * 128 + (lane & 31), b_row0 = wc * 64 + (lane & 31);
-    const int a_base_off = a_row0 * 128, b_base_off = Q_A_BYTES + b_row0 * 128;
-    const int a_swz = (a_row0 >> 1) & 7, b_swz = (b_row0 >> 1) & 7;
+    // fragment offsets of k-step 0 (gemm_common.h, frag_off): the W rows are the MFMAs' row side (permuted rows), the A rows their column side
+    const int a_frag_off = frag_off<false>(grp * 128, lane), b_frag_off = Q_A_BYTES + frag_off<true>(wc * 64, lane);
 
     // prologue: B(0) (+ bias), A(0), B(1) requested; K-tile 0 landed (B(1) may stay in flight)
     stage_B(); stage_A(); stage_B();
@@ -228,13 +230,11 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(GemmP p) {
     };
     while (true) {
         tile_stamp(0);
-        f32x16 acc[4][2];
+        AccBlock blk[4][2];                           // 16x16x32 accumulators inside the K loop (gemm_common.h); the epilogues' f32x16 layout after it
 #pragma unroll
         for (int i = 0; i < 4; i++)
 #pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+            for (int j = 0; j < 2; j++) acc_block_zero(blk[i][j]);
         int tm, tn; decode(item, tm, tn);
         const int64_t cm0 = (int64_t)tm * QBM, cn0 = (int64_t)tn * QBN;
         if (!STAGGERED_EPI && grp == 1) q_bar();     // (re-)create the one-barrier offset
@@ -252,23 +252,21 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(GemmP p) {
                     }
                 }
             };
-            bf16x8 fa[2][4], fb[2][4];                // [row tile of the phase][kc], [j][kc]
+            bf16x8 fa[2][4], fb[2][4];                // [row tile of the phase][2 s + half], [j][2 s + half]: k-step s, 16-row half (gemm_common.h, frag_read)
             auto ld_a = [&](int ih) {
 #pragma unroll
                 for (int t = 0; t < 2; t++)
 #pragma unroll
-                    for (int kc = 0; kc < 4; kc++)
-                        fa[t][kc] = *(const bf16x8*)(tb + a_base_off + (2 * ih + t) * 4096 + (((kc * 2 + hi) ^ a_swz) << 4));
+                    for (int x = 0; x < 4; x++) fa[t][x] = frag_read(tb + (2 * ih + t) * 4096, a_frag_off, x >> 1, x & 1);
             };
-            auto mma = [&](int ih) {                   // 16 MFMAs, four independent chains (kc outer: every chain sees kc = 0..3 in order)
+            auto mma = [&](int ih) {                   // 32 MFMAs on four 32 x 32 blocks (k-step outer: every accumulator sees k-step 0, then 1)
                 __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-                for (int kc = 0; kc < 4; kc++)
+                for (int s = 0; s < 2; s++)
 #pragma unroll
                     for (int t = 0; t < 2; t++)
 #pragma unroll
-                        for (int j = 0; j < 2; j++)
-                            acc[2 * ih + t][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][kc], fa[t][kc], acc[2 * ih + t][j], 0, 0, 0);
+                        for (int j = 0; j < 2; j++) mma_block_step(blk[2 * ih + t][j], fb[j], fa[t], s);
                 __builtin_amdgcn_s_setprio(0);
             };
             // ---- phase A ----
@@ -277,7 +275,7 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(GemmP p) {
 #pragma unroll
             for (int j = 0; j < 2; j++)
 #pragma unroll
-                for (int kc = 0; kc < 4; kc++) fb[j][kc] = *(const bf16x8*)(tb + b_base_off + j * 4096 + (((kc * 2 + hi) ^ b_swz) << 4));
+                for (int x = 0; x < 4; x++) fb[j][x] = frag_read(tb + j * 4096, b_frag_off, x >> 1, x & 1);
             ld_a(0);
             }
             if (a_early) a_early = false;             // (requested ahead of the previous tile's epilogue)
@@ -324,6 +322,11 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(GemmP p) {
             cur ^= 1;
         }
         tile_stamp(2);
+        f32x16 acc[4][2];                             // the blocks in the 32x32x16 accumulator layout the epilogues take: 8 v_permlane16_swap per block
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 2; j++) acc[i][j] = acc_block_32x32(blk[i][j]);
         if (!STAGGERED_EPI && grp == 0) q_bar();     // let group 1 finish its last MFMA phase: epilogues run together
         const bool inner = (cm0 + QBM <= p.M) && (cn0 + QBN <= p.N);
         // The next tile's K-tile 1 goes into the buffer the last K-tile just left (its A rows: both groups are past LOAD B).  Its A pieces are

@@ -5,10 +5,10 @@
 // whole rounds to the 256 x 256 kernel and the remaining row tiles to THIS kernel, split into half-height tiles: 99 tiles become 198
 // workgroups of 128 x 256, one round of about 0.56 tile times instead of a whole one (3.39 -> 3.56 instead of 4 rounds).
 //
-// Same operands, same LDS image (LDS-DMA, 16-byte chunk XOR swizzle), same MFMA shape and K order, same epilogue code as gemm_pp2.hip
+// Same operands, same LDS image (LDS-DMA, 16-byte chunk XOR swizzle), same MFMA block primitive and K order, same epilogue code as gemm_pp2.hip
 // -> bit-identical outputs (tests/test_determinism_gpu.py).  Schedule: 8 waves = two groups of four (group g = output rows g*64..+64,
 // wave wc = 64-column slice; every SIMD hosts one wave of each group); a K-tile is TWO quadrant phases (64x32 of the wave's 64x64
-// output: 8 MFMAs of 32x32x16), each split by barriers into a LOAD half and an MFMA half; group 1 runs one barrier behind group 0, so
+// output: two 32 x 32 blocks = 16 MFMAs of 16x16x32, gemm_common.h), each split by barriers into a LOAD half and an MFMA half; group 1 runs one barrier behind group 0, so
 // one group owns the matrix pipe while the other waits for LDS / issues DMA:
 //
 //   half-slot:      4c           4c+1          4c+2          4c+3
@@ -46,9 +46,8 @@ __global__ __launch_bounds__(512) void gemm_pph_kernel(GemmP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int hi = lane >> 5;
     const int grp = w >> 2, wc = w & 3;
-    const int nk = (int)(p.K / HBK);                 // >= 2 (host checks)
+    const int nk = (int)(p.K / HBK);                // >= 2 (host checks)
     const int nitems = p.tiles_m * p.tiles_n;
     const int item = xcd_remap(blockIdx.x, nitems);
     if (item >= nitems) return;
@@ -103,10 +102,8 @@ __global__ __launch_bounds__(512) void gemm_pph_kernel(GemmP p) {
         return 4;
     };
 
-    // fragment addresses: A rows grp*64 + t*32 + (lane&31), B rows wc*64 + j*32 + (lane&31); one swizzle per operand
-    const int a_row0 = grp * 64 + (lane & 31), b_row0 = wc * 64 + (lane & 31);
-    const int a_base_off = a_row0 * 128, b_base_off = b_row0 * 128;
-    const int a_swz = (a_row0 >> 1) & 7, b_swz = (b_row0 >> 1) & 7;
+    // fragment offsets of k-step 0 (gemm_common.h, frag_off): A rows grp*64 + t*32 + ... are the MFMAs' column side, B rows wc*64 + j*32 + ... their row side
+    const int a_frag_off = frag_off<false>(grp * 64, lane), b_frag_off = frag_off<true>(wc * 64, lane);
 
     // prologue: A(0), B(0) [+bias], A(1), B(1); retire A(0) and B(0), K-tile 1 stays in flight
     stage_A(0, 0);
@@ -116,37 +113,34 @@ __global__ __launch_bounds__(512) void gemm_pph_kernel(GemmP p) {
     ph_wait<6>();
     ph_bar();
 
-    f32x16 acc[2][2];
+    AccBlock blk[2][2];                               // 16x16x32 accumulators inside the K loop (gemm_common.h)
 #pragma unroll
     for (int i = 0; i < 2; i++)
 #pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+        for (int j = 0; j < 2; j++) acc_block_zero(blk[i][j]);
     if (grp == 1) ph_bar();                           // create the one-barrier offset between the groups
     int cur = 0, bcur = 0;                            // A stage (kt & 1), B stage (kt % 3)
     for (int kt = 0; kt < nk; kt++) {
         const unsigned char* ta = lds + H_A_OFF + cur * H_A_BYTES;
         const unsigned char* tbb = lds + H_B_OFF + bcur * H_B_BYTES;
         const int bnext2 = bcur >= 1 ? bcur - 1 : 2;  // (kt + 2) % 3
-        bf16x8 fa[2][4], fb[2][4];                    // [32-row tile][kc], [j][kc]
+        bf16x8 fa[2][4], fb[2][4];                    // [32-row tile][2 s + half], [j][2 s + half]: k-step s, 16-row half (gemm_common.h, frag_read)
         auto ld_a = [&]() {
 #pragma unroll
             for (int t = 0; t < 2; t++)
 #pragma unroll
-                for (int kc = 0; kc < 4; kc++) fa[t][kc] = *(const bf16x8*)(ta + a_base_off + t * 4096 + (((kc * 2 + hi) ^ a_swz) << 4));
+                for (int x = 0; x < 4; x++) fa[t][x] = frag_read(ta + t * 4096, a_frag_off, x >> 1, x & 1);
         };
         auto ld_b = [&](int j) {
 #pragma unroll
-            for (int kc = 0; kc < 4; kc++) fb[j][kc] = *(const bf16x8*)(tbb + b_base_off + j * 4096 + (((kc * 2 + hi) ^ b_swz) << 4));
+            for (int x = 0; x < 4; x++) fb[j][x] = frag_read(tbb + j * 4096, b_frag_off, x >> 1, x & 1);
         };
-        auto mma = [&](int j) {
+        auto mma = [&](int j) {                       // 16 MFMAs on two 32 x 32 blocks (k-step outer)
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int kc = 0; kc < 4; kc++)
+            for (int s = 0; s < 2; s++)
 #pragma unroll
-                for (int t = 0; t < 2; t++)
-                    acc[t][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j][kc], fa[t][kc], acc[t][j], 0, 0, 0);
+                for (int t = 0; t < 2; t++) mma_block_step(blk[t][j], fb[j], fa[t], s);
             __builtin_amdgcn_s_setprio(0);
         };
         // ---- q0: the B stage of K-tile kt-1 is free (both groups are past q1 LOAD of that K-tile): it takes K-tile kt+2 ----
@@ -169,6 +163,11 @@ __global__ __launch_bounds__(512) void gemm_pph_kernel(GemmP p) {
         cur ^= 1;
         bcur = bcur == 2 ? 0 : bcur + 1;
     }
+    f32x16 acc[2][2];                                 // the blocks in the 32x32x16 accumulator layout the epilogues take
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) acc[i][j] = acc_block_32x32(blk[i][j]);
     if (grp == 0) ph_bar();                           // let group 1 finish its last MFMA half: epilogues run together
 
     const bool inner = (cm0 + HBM <= p.M) && (cn0 + HBN <= p.N);
