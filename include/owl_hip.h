@@ -311,6 +311,16 @@ int owl_grad_norm_workspace_bytes(int64_t n, int64_t* bytes);
 int owl_grad_sumsq(void* stream, const float* g, int64_t n, void* workspace);
 int owl_adamw_step_grouped(void* stream, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale, const int64_t* seg_end, const float* seg_lr, const float* seg_wd, int nseg, float max_norm, const void* workspace, float* norm_out);
 
+/* ---- exponential moving average of the trainable bucket (still ABI 8: additive; optim.py, csrc/optim_ema.hip) --------------------------------------------------
+ *   owl_ema_update      ema[i] = fma(d, ema[i], w * p[i]) on `stream`: exactly two f32 roundings per element (round-to-nearest intrinsics, whatever the
+ *                       contraction flags).  d and w are formed by the caller: w = 1 - d, taken in double from the f32 d and rounded to f32.  n % 4 == 0;
+ *                       no scratch, no atomics.  d = 0 (w = 1) gives ema == p and d = 1 (w = 0) leaves ema unchanged, bit for bit, for finite inputs.
+ *   owl_adamw_step_ema  owl_adamw_step_grouped (same arguments, same clip prologue, same segment table, same bits in p / m / v / p_bf16) with the line
+ *                       above applied to the just-updated parameter before it is stored: one more f32 stream in and one out, p is not read again.
+ *                       Here a null seg_end means one segment over everything with the scalar `lr` / `weight_decay` (nseg is then ignored).           */
+int owl_ema_update(void* stream, float* ema, const float* p, int64_t n, float d, float w);
+int owl_adamw_step_ema(void* stream, float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale, const int64_t* seg_end, const float* seg_lr, const float* seg_wd, int nseg, float max_norm, const void* workspace, float* norm_out, float* ema, float d, float w);
+
 /* ---- frozen-prefix activation cache (still ABI 8: additive; prefix_cache.py, csrc/prefix_cache.hip) -------------------------------------------------------------
  * Under a freeze rule the residual stream that the first non-frozen consumer normalises depends on the pixels alone: it is kept per image (f32 blocks of
  * block_elems = Tp D elements) and the frozen layers below it are skipped for images already kept.

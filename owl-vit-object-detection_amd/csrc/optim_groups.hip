@@ -3,37 +3,7 @@
 //   grad_sumsq_kernel     one read of the gradient bucket -> one f64 partial sum of squares per workgroup (fixed order, no atomics)
 //   adamw_grouped_kernel  every workgroup adds the partials in ONE fixed order (identical bits everywhere), forms the clip coefficient and runs
 //                         adamw_kernel's arithmetic with lr / weight_decay taken per segment of the bucket from a table passed by value
-#include "common.h"
-
-#define OWL_OPT_MAX_SEGS 32
-#define SUMSQ_MAX_BLOCKS 1024      // <= 256 * SUMSQ_PER_THREAD: the step's prologue reads SUMSQ_PER_THREAD partials per thread
-#define SUMSQ_PER_THREAD 4
-
-struct SegTable {
-    int64_t end[OWL_OPT_MAX_SEGS];     // exclusive end offset of segment s (elements; multiples of 4, strictly increasing, end[nseg-1] == n)
-    float lr[OWL_OPT_MAX_SEGS];
-    float wd[OWL_OPT_MAX_SEGS];
-};
-
-// xor butterfly: a + b is commutative, so lanes l and l ^ o hold the same bits after every stage -- the order is fixed by the lane ids alone
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// lanes (butterfly), then the four waves through LDS in wave order; the result is valid in every thread
-__device__ __forceinline__ double block_sum_f64(double v, double* wsum) {
-    v = wave_sum_f64(v);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
-
-static inline int64_t sumsq_blocks(int64_t n) {
-    int64_t blocks = (n / 4 + 255) / 256;
-    return blocks > SUMSQ_MAX_BLOCKS ? SUMSQ_MAX_BLOCKS : blocks;
-}
+#include "optim_common.h"          // SegTable, block_sum_f64, sumsq_blocks: shared with optim_ema.hip
 
 __device__ __forceinline__ double sq_acc(double acc, const float4& x) {
     acc = fma((double)x.x, (double)x.x, acc);

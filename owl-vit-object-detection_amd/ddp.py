@@ -173,6 +173,10 @@ class DataParallel:
             broadcast_flat(model.flat_param, 0, group)
             if hasattr(model, "refresh_compute_weights"):
                 model.refresh_compute_weights(force=True)
+            # an average seeded at the optimizer's construction (optim.FusedAdamW(ema_decay=)) holds THIS rank's pre-broadcast weights: start it from
+            # the broadcast ones, like the parameters.  One already updated (a resumed run) is left alone.  No collective: every rank then computes the same bits.
+            if getattr(optimizer, "ema", None) is not None and optimizer.ema_updates == 0:
+                optimizer.ema.copy_(model.flat_param.detach())
         self.overlap = bool(overlap) and model.flat_grad.is_cuda and self.fused
         if self.overlap:
             model.overlap_tail = True                   # backward, all-reduce and AdamW all run on the model's tail stream
