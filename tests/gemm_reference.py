@@ -564,6 +564,7 @@ def sample_rows(M, M_main):
 
 
 SHAPES = [(1, 8, 64), (127, 136, 128), (129, 264, 192), (300, 256, 192), (513, 520, 256), (130, 264, 4096), (2900, 1000, 128)]
+TOWER_SHAPES = [(35, 192, 64), (35, 128, 128)]      # the text tower's row count at N = 5, S = 7 (tests/test_text_reference_gpu.py) with K = width of tiny / small
 TALL = (76700, 256, 128)       # N = 248 of the first draft fails the dispatcher's N >= 256: the nearest shape with 300 x 1 tiles of 256
 LAYOUT_SHAPES = [(129, 264, 192), (513, 520, 256)]
 TILES = (128, 256, 7, 0, 6)
@@ -598,7 +599,7 @@ def cases():
     out = []
     for fi, (name, epi, *_rest) in enumerate(FORMS):
         pl = profiles_of(epi)
-        for si, (M, N, K) in enumerate(SHAPES):
+        for si, (M, N, K) in enumerate(SHAPES + TOWER_SHAPES):
             out.append((M, N, K, name, pl[(si + fi) % len(pl)]))
             if M * N < 200000:
                 out.append((M, N, K, name, pl[(si + fi + 2) % len(pl)]))

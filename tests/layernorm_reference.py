@@ -740,7 +740,7 @@ def emulate_merge_bwd(dfeats, x, cls_ln, st1, st2, g1, b1, g2, old=None, hooks=(
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # the case set shared by the CPU and the GPU test
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-WIDTHS = (4, 128, 252, 260, 768, 1020, 1024)
+WIDTHS = (4, 128, 252, 260, 768, 1020, 1024, 64, 512)     # (64, 512: the text tower's widths, last so that the rotation of merge_cases stays)
 FULL_WIDTHS = (260, 768, 1024)            # every profile; the other widths take randn + outlier
 FWD_ROWS = (1, 5, 67)
 BWD_ROWS = (1, 67, 131)

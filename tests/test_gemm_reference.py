@@ -69,7 +69,7 @@ def test_shapes_reach_the_kernels_named():
     assert {65535, 65536}.issubset(rows) and {r // 128 for r in rows} == set(range((M + 127) // 128))
     # every shape x tile lands on a kernel of the family, and the case set holds every form at every shape
     assert {k for (M, N, K) in R.SHAPES for t in R.TILES for e in R.EPI_NAMES for (k, _) in R.dispatch_path(e, M, N, K, t)} == {"pp2", "pph", "sp128", "sp256"}
-    assert {(M, N, K, f) for (M, N, K, f, _) in R.cases()} == {(M, N, K, f[0]) for (M, N, K) in R.SHAPES for f in R.FORMS}
+    assert {(M, N, K, f) for (M, N, K, f, _) in R.cases()} == {(M, N, K, f[0]) for (M, N, K) in R.SHAPES + R.TOWER_SHAPES for f in R.FORMS}
     for epi in R.EPI_NAMES:
         for p in R.profiles_of(epi):
             assert sum(1 for (_, _, _, f, q) in R.cases() if R.FORM[f][1] == epi and q == p) >= 2, (epi, p)
