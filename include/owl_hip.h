@@ -32,7 +32,7 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's); still 8, additive again: + owl_gemm_nt_plan and the OWL_GEMM_KERNEL_* ids (which kernels a GEMM call launches; host query); still 8, additive again: + owl_prefix_emit, owl_prefix_gather (the frozen-prefix activation cache).  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's); still 8, additive again: + owl_gemm_nt_plan and the OWL_GEMM_KERNEL_* ids (which kernels a GEMM call launches; host query); still 8, additive again: + owl_prefix_emit, owl_prefix_gather (the frozen-prefix activation cache); still 8, additive again: + owl_image_query_workspace_bytes, owl_image_query_select, owl_query_bank_fill (the query bank from image exemplars).  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
 #define OWL_ABI_VERSION 8
 const char* owl_last_error(void);
@@ -334,6 +334,32 @@ int owl_adamw_step_ema(void* stream, float* p, const float* g, float* m, float* 
  * scratch: pure streams.                                                                                                                            */
 int owl_prefix_emit(void* stream, const float* xs, const void* delta1_bf16, const void* delta2_bf16, int64_t n, int64_t block_elems, const int64_t* dst_addr, const int64_t* slot_addr);
 int owl_prefix_gather(void* stream, int64_t n, int64_t block_elems, const int64_t* src_addr, const int64_t* dst_addr);
+
+/* ---- query bank from image exemplars (still ABI 8: additive; csrc/image_query.hip, models.OwlViT.embed_image_query / set_queries_from_exemplars) ----
+ * OWL-ViT's image-conditioned query (HF5:1246-1288 `embed_image_query`), extended from HF's hard-wired whole image to a query box inside the example
+ * image.  Initialisation-time entries: they run once, outside every step.
+ *   owl_image_query_select   per exemplar n of N:  e f32 [N, P, Dt] (the class head's un-normalised dense0 output), boxes f32 [N, P, 4] corners,
+ *       qbox f32 [N, 4] corners normalised to the processed image (NULL = [0, 0, 1, 1] for every exemplar: HF's literal rule).  HF's rule, quirks kept:
+ *         1. iou_p = box_iou(qbox, boxes_p) in f32, one rounding per written operation (contraction off): both areas, lt = max, rb = min,
+ *            wh = clamp(rb - lt, 0), inter, union = (area_q + area_p) - inter, inter / union;
+ *         2. every iou_p == 0: v_p = iou_p - (hull_p - union_p) / hull_p (generalized_box_iou), else v_p = iou_p;
+ *         3. thr = fl32(max_p v_p * 0.8f), selected = {p : v_p >= thr}; a negative maximum selects nothing (HF drops the image; here: EMPTY), after the
+ *            fallback v_p <= 0, so only an exactly touching box (v_p == 0) is selected; a NaN v_p (zero-area box or hull) gives EMPTY, as torch.max would;
+ *         4. mean_k = (sum over ALL p of e[p, k]) / P;   5. sim_p = sum_k mean_k e[p, k] for selected p;
+ *         6. best = the selected p of smallest sim_p, the LOWEST p on a tie (torch.argmin).
+ *       Steps 4 to 6 accumulate in float64 (f32 widened, f64 adds / FMAs, one fixed order -- as owl_grad_sumsq and the mAP IoU do): with f32 accumulation
+ *       the worst-case error of a P-term column sum through a Dt-term dot is 1e-4 .. 5e-2 at P = 3600, Dt = 768, above the argmin margins of random
+ *       inputs (2.5e-4), so no derived bound could decide the argmin; in f64 it is ~1e-13 and the kernels are bandwidth-bound either way.
+ *       Outputs: best i32 [N] (-1 = empty); query f32 [N, Dt] = e[n, best] bit for bit (zeros when empty); info i32 [N, 2] = (flags: bit 0 fallback
+ *       taken, bit 1 empty; number selected); optional diagnostics v_out f32 [N, P], mean_out f64 [N, Dt], sim_out f64 [N, P] (+inf where not selected).
+ *       workspace: device scratch of owl_image_query_workspace_bytes(N, P, Dt) bytes (f64 column-sum partials, one per 64 rows); nothing is allocated.
+ *       1 <= N <= 2^20, 1 <= P <= 8192, Dt % 4 == 0, Dt <= 1024; rows 16-byte aligned.  Two launches, no atomics, no host sync, bitwise reproducible.
+ *   owl_query_bank_fill      query f32 [N, Dt]; a CSR assignment row_ptr i32 [nq + 1], members i32 (exemplar indices, ascending within a row), both on
+ *       the DEVICE; bank f32 [nq, Dt].  Every row r with members: bank[r] = unit(sum over its members, ascending, of unit(query_m)), unit(x) = x / |x|,
+ *       norms and sums in f64, ONE rounding to f32.  Rows without members are not touched.  One workgroup per row, no atomics.  nq <= 1152, Dt as above. */
+int owl_image_query_workspace_bytes(int64_t N, int64_t P, int64_t Dt, int64_t* nbytes);
+int owl_image_query_select(void* stream, const float* e, const float* boxes, const float* qbox, int64_t N, int64_t P, int64_t Dt, void* workspace, int64_t workspace_bytes, int* best, float* query, int* info, float* v_out, double* mean_out, double* sim_out);
+int owl_query_bank_fill(void* stream, const float* query, const int* row_ptr, const int* members, float* bank, int64_t N, int64_t nq, int64_t Dt);
 
 /* ---- utilities ------------------------------------------------------------------------------------ */
 int owl_cast_f32_bf16(void* stream, const float* in, void* out, int64_t n);

@@ -856,9 +856,130 @@ class OwlViT(nn.Module):
             boxes, sims = self._forward_impl(image, save=False, ids=ids)
         return (boxes, None, sims, None)
 
+    # -- query bank from image exemplars ---------------------------------------------------------------------
+    def _embed_image_query(self, pixel_values, query_boxes):
+        cfg, dev = self.cfg, self.device_
+        P, Dt = cfg.patches, cfg.text_dim
+        N = int(pixel_values.shape[0])
+        if N < 1:
+            raise ValueError("embed_image_query: no images")
+        qb = None
+        if query_boxes is not None:
+            qb = torch.as_tensor(query_boxes, dtype=torch.float32).to(dev).contiguous()
+            if tuple(qb.shape) != (N, 4):
+                raise ValueError(f"embed_image_query: query_boxes must be [{N}, 4] normalised corners (x0, y0, x1, y1), got {tuple(qb.shape)}")
+        self._wait_params()
+        queries, best, boxes, info = [], [], [], []
+        # at most two batch sizes are new to the workspace cache (full chunks and the last one): with the limit raised by two for the length of this call
+        # no size is evicted by it, so a recording forward's pending backward still finds its activations
+        keep = self.max_cached_batch_sizes
+        self.max_cached_batch_sizes = max(1, int(keep)) + 2
+        try:
+            for a in range(0, N, EXEMPLAR_CHUNK):
+                nb = min(EXEMPLAR_CHUNK, N - a)
+                pb, _ = self._forward_impl(pixel_values[a:a + nb], save=False)
+                e = self._workspace(nb, train=False)["e"]          # the class head's dense0 output of this chunk: read before the next chunk overwrites it
+                b, q, i = ops.image_query_select(e, pb, None if qb is None else qb[a:a + nb], nb, P, Dt)
+                queries.append(q); best.append(b); boxes.append(pb); info.append(i)
+        finally:
+            self.max_cached_batch_sizes = keep
+        cat = (lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts))
+        return cat(queries), cat(best).to(torch.int64), cat(boxes), cat(info)
+
+    @torch.no_grad()
+    def embed_image_query(self, pixel_values, query_boxes=None):
+        """OWL-ViT's image-conditioned query (HF `OwlViTForObjectDetection.embed_image_query`, same names and return order): for each example image, among
+        the predicted boxes whose IoU with the query box is within 80 % of the best, the one whose class embedding is least like the image's mean
+        embedding; its un-normalised class embedding is the query.  -> (query_embeds [N, Dt] f32, box_indices [N] int64, pred_boxes [N, P, 4]).
+
+        query_boxes: [N, 4] normalised corners (x0, y0, x1, y1) of the annotated object inside each processed image, on any device; None = the whole
+        image, which is the rule HF hard-wires.  HF's quirks are kept (csrc/image_query.hip): when no box overlaps, the generalized IoU decides and only
+        an exactly touching box can be selected; an image HF would silently drop is reported with index -1 and a zero embedding.
+
+        Runs without grad on the EVAL workspace (a pending training backward is not disturbed), behind a deferred optimizer tail, in chunks of at
+        most 32 images; no host sync.  The frozen-prefix cache is neither read nor written."""
+        return self._embed_image_query(pixel_values, query_boxes)[:3]
+
+    @torch.no_grad()
+    def set_queries_from_exemplars(self, pixel_values, class_ids, query_boxes=None):
+        """Initialise the query bank from annotated example images: exemplar n (pixel_values[n], optionally its object's box query_boxes[n]) belongs to
+        class class_ids[n].  The exemplars of a class are numbered k = 0, 1, ... in the order given; slot s in {0, 1, 2} of class c (bank row 3 c + s)
+        becomes the unit mean of the unit queries {k : k % 3 == s}, or, when that set is empty, of exemplar s % n_c (exemplar_slots).  A class without
+        exemplars keeps its three rows, bit for bit -- a text prior stays where no image prior is given.
+
+        Writes the `queries` parameter in place (one kernel, on its flat-bucket view).  Reading the selection back is ONE host sync: this is
+        initialisation and never runs inside a step.  Call it BEFORE constructing FusedAdamW / ddp.DataParallel: Adam moments and an EMA are not
+        rewritten (under data parallel every rank computes the same bits from the same exemplars, or the wrapper broadcasts rank 0's bank as it does
+        today).  The frozen-prefix cache stays valid: the bank sits above it.
+
+        Raises ValueError naming the exemplar and its class when a class id is outside [0, C), a box is not x0 < x1, y0 < y1, or a selection is empty
+        (no predicted box overlaps or touches the query box); RuntimeError inside `optimizer.ema_weights()`.
+        -> dict(box_indices [N], n_selected [N], fallback [N] (lists of int / bool), slots = the 3 C member lists)."""
+        if getattr(self, "_ema_scope", False):
+            raise RuntimeError("set_queries_from_exemplars inside `with ema_weights():` -- the bucket holds the averaged weights and the raw iterate is stashed: "
+                               "leave the scope first")
+        cfg = self.cfg
+        ids = check_exemplars(class_ids, query_boxes, int(pixel_values.shape[0]), cfg.n_classes)
+        table = exemplar_slots(ids, cfg.n_classes)
+        query, best, _, info = self._embed_image_query(pixel_values, query_boxes)
+        host = torch.cat([best.view(-1, 1).to(torch.int32), info], 1).cpu().tolist()          # the one sync
+        for n, (b, flags, nsel) in enumerate(host):
+            if b < 0 or flags & 2:
+                raise ValueError(f"set_queries_from_exemplars: exemplar {n} (class {ids[n]}) selects no predicted box: none overlaps or exactly touches its "
+                                 "query box")
+        row_ptr, members = slots_csr(table)
+        dev = self.device_
+        bank = self._byname["queries"].data.view(cfg.queries, cfg.text_dim)
+        ops.query_bank_fill(query, torch.from_numpy(row_ptr).to(dev), torch.from_numpy(members).to(dev), bank, len(ids), cfg.queries, cfg.text_dim)
+        self._bf16_current = False          # a raw-pointer write the bucket's version counter does not see: the next forward recasts the bf16 copy
+        return dict(box_indices=[h[0] for h in host], n_selected=[h[2] for h in host], fallback=[bool(h[1] & 1) for h in host], slots=table)
+
+
+EXEMPLAR_CHUNK = 32          # images per forward of embed_image_query
+
+
+def exemplar_slots(class_ids, n_classes):
+    """The slot rule of set_queries_from_exemplars, a pure host function: -> 3 C lists of exemplar indices (ascending), list 3 c + s = the members of slot
+    s of class c.  With the exemplars of class c numbered k = 0, 1, ... in the order given, slot s takes {k : k % 3 == s} when that set is not empty and
+    exemplar s % n_c otherwise; the three lists of a class without exemplars are empty (its rows are kept)."""
+    per = [[] for _ in range(int(n_classes))]
+    for n, c in enumerate(class_ids):
+        per[int(c)].append(n)
+    table = []
+    for mem in per:
+        for s in range(3):
+            table.append([] if not mem else (mem[s::3] or [mem[s % len(mem)]]))
+    return table
+
+
+def slots_csr(table):
+    """A slot table (exemplar_slots) as the CSR arrays owl_query_bank_fill takes: (row_ptr int32 [rows + 1], members int32, at least one entry)."""
+    row_ptr = np.zeros(len(table) + 1, dtype=np.int32)
+    row_ptr[1:] = np.cumsum([len(m) for m in table])
+    members = np.asarray([n for m in table for n in m] or [0], dtype=np.int32)
+    return row_ptr, members
+
+
+def check_exemplars(class_ids, query_boxes, n_images, n_classes):
+    """Host-side validation of an exemplar set -> the class ids as a list of int.  Raises ValueError naming the exemplar and its class."""
+    ids = [int(c) for c in (class_ids.tolist() if hasattr(class_ids, "tolist") else class_ids)]
+    if len(ids) != n_images or not ids:
+        raise ValueError(f"exemplars: {n_images} images for {len(ids)} class ids (one class id per example image, at least one)")
+    for n, c in enumerate(ids):
+        if not 0 <= c < n_classes:
+            raise ValueError(f"exemplars: exemplar {n} has class {c}, outside [0, {n_classes})")
+    if query_boxes is not None:
+        qb = torch.as_tensor(query_boxes, dtype=torch.float32).cpu()
+        if tuple(qb.shape) != (n_images, 4):
+            raise ValueError(f"exemplars: query_boxes must be [{n_images}, 4] normalised corners (x0, y0, x1, y1), got {tuple(qb.shape)}")
+        for n, (x0, y0, x1, y1) in enumerate(qb.tolist()):
+            if not (x0 < x1 and y0 < y1):          # (a NaN fails too)
+                raise ValueError(f"exemplars: exemplar {n} (class {ids[n]}) has query box ({x0:g}, {y0:g}, {x1:g}, {y1:g}): corners need x0 < x1 and y0 < y1")
+    return ids
+
 
 def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed: int = 1234, state=None, *,
-               prompt_ids=None, text_state=None, vocab=None, merges=None, trainable=None, image_size=None):
+               prompt_ids=None, text_state=None, vocab=None, merges=None, trainable=None, image_size=None, exemplars=None):
     """ref src/models.py:149-191.  The reference downloads `google/owlvit-base-patch32` and runs the
     CLIP text tower once to initialise the query bank; neither box has network access, so weights
     come from `state` (name -> array, reference parameter names) or, by default, the deterministic
@@ -881,7 +1002,11 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
     `image_size` (None = the architecture's): the square input size the model is built for, a multiple of the patch size with at most 8192 patches
     (HF's `interpolate_pos_encoding=True`, HF5:296-332).  The native grid of the position table is read off `state`'s table (a checkpoint's, through
     weights.from_hf_state_dict) or is the architecture's; the parameter keeps that shape and the embeddings read a bicubic resample of it, so
-    state dicts and FusedAdamW states move freely between sizes.  At the native size nothing changes."""
+    state dicts and FusedAdamW states move freely between sizes.  At the native size nothing changes.
+
+    `exemplars` (None = nothing new runs or is allocated): `(pixel_values, class_ids[, query_boxes])`, annotated example images at the model's input size --
+    the image prior for classes a short prompt does not describe.  Applied after construction, hence after the text initialisation when `prompt_ids=` /
+    `vocab=` is given too (OwlViT.set_queries_from_exemplars): classes with exemplars take the image prior, the others keep the text (or random) one."""
     n_classes = len(labelmap)
     cfg = get_config(arch, n_classes=n_classes)
     g0 = table_grid(np.asarray(state[_POS]).shape[0]) if (state is not None and _POS in state) else cfg.grid
@@ -912,4 +1037,9 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
         state = OrderedDict(state)
         state["queries"] = tower.query_bank(ids).cpu().numpy()
         del tower
-    return OwlViT(cfg, state, device, trainable=trainable)
+    model = OwlViT(cfg, state, device, trainable=trainable)
+    if exemplars is not None:
+        if not 2 <= len(exemplars) <= 3:
+            raise ValueError("load_model: exemplars= is (pixel_values, class_ids) or (pixel_values, class_ids, query_boxes)")
+        model.set_queries_from_exemplars(*exemplars)
+    return model

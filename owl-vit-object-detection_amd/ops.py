@@ -446,3 +446,39 @@ def colsum_bf16(src, colsum, rows, cols, partials=None):
     _chk(src, torch.bfloat16, "src"); _chk(colsum, torch.float32, "colsum")
     part = _part(partials, rows, cols, src.device)
     _lib.call("owl_colsum_bf16", stream(), src, src.shape[-1], colsum, rows, cols, part, part.numel())
+
+
+# ---- query bank from image exemplars (csrc/image_query.hip): initialisation-time, outside every step ----
+def image_query_workspace_bytes(N, P, Dt) -> int:
+    """Bytes of device scratch image_query_select needs (the f64 column-sum partials); a host query, no device call."""
+    nbytes = torch.zeros(1, dtype=torch.int64)
+    _lib.call("owl_image_query_workspace_bytes", N, P, Dt, nbytes)
+    return int(nbytes.item())
+
+
+def image_query_select(e, boxes, qbox, N, P, Dt, diagnostics=False):
+    """HF's `embed_image_query` selection per exemplar (include/owl_hip.h): e f32 [>= N P, Dt] (the class head's un-normalised dense0 output), boxes f32
+    [N, P, 4] corners, qbox f32 [N, 4] corners or None (= the whole image).  -> (best i32 [N] (-1 = empty), query f32 [N, Dt] = e[n, best] bit for bit,
+    info i32 [N, 2] = (flags: bit 0 fallback, bit 1 empty; number selected)); with diagnostics=True also (v f32 [N, P], mean f64 [N, Dt], sim f64 [N, P]).
+    No host sync."""
+    _chk(e, torch.float32, "e"); _chk(boxes, torch.float32, "boxes"); _chk(qbox, torch.float32, "qbox")
+    if e.numel() < N * P * Dt or boxes.numel() < N * P * 4 or (qbox is not None and qbox.numel() != N * 4):
+        raise ValueError("image_query_select: e must hold [N, P, Dt], boxes [N, P, 4], qbox [N, 4]")
+    dev = e.device
+    ws = torch.empty(image_query_workspace_bytes(N, P, Dt), dtype=torch.uint8, device=dev)
+    best = torch.empty(N, dtype=torch.int32, device=dev)
+    query = torch.empty(N, Dt, dtype=torch.float32, device=dev)
+    info = torch.empty(N, 2, dtype=torch.int32, device=dev)
+    diag = (torch.empty(N, P, dtype=torch.float32, device=dev), torch.empty(N, Dt, dtype=torch.float64, device=dev),
+            torch.empty(N, P, dtype=torch.float64, device=dev)) if diagnostics else (None, None, None)
+    _lib.call("owl_image_query_select", stream(), e, boxes, qbox, N, P, Dt, ws, ws.numel(), best, query, info, *diag)
+    return (best, query, info) + (diag if diagnostics else ())
+
+
+def query_bank_fill(query, row_ptr, members, bank, N, nq, Dt):
+    """bank [nq, Dt] f32, in place: every row r with members <- unit(sum over members[row_ptr[r] : row_ptr[r + 1]], ascending, of unit(query_m)); rows
+    without members keep their bits.  row_ptr i32 [nq + 1] and members i32 are device tensors (models.slots_csr builds them on the host)."""
+    _chk(query, torch.float32, "query"); _chk(row_ptr, torch.int32, "row_ptr"); _chk(members, torch.int32, "members"); _chk(bank, torch.float32, "bank")
+    if query.numel() < N * Dt or row_ptr.numel() != nq + 1 or bank.numel() < nq * Dt or members.numel() < 1:
+        raise ValueError("query_bank_fill: query must hold [N, Dt], row_ptr [nq + 1], bank [nq, Dt], members at least one index")
+    _lib.call("owl_query_bank_fill", stream(), query, row_ptr, members, bank, N, nq, Dt)

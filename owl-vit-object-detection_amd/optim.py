@@ -101,10 +101,12 @@ class _EmaState:
             self._ema_stash.copy_(m.flat_param)
             m.flat_param.copy_(self.ema)
         self._ema_active = True
+        m._ema_scope = True          # (models.OwlViT.set_queries_from_exemplars refuses to write the bank while it holds the average)
         try:
             yield m
         finally:
             self._ema_active = False
+            m._ema_scope = False
             with torch.no_grad():
                 m.flat_param.copy_(self._ema_stash)
 
