@@ -361,6 +361,25 @@ int owl_image_query_workspace_bytes(int64_t N, int64_t P, int64_t Dt, int64_t* n
 int owl_image_query_select(void* stream, const float* e, const float* boxes, const float* qbox, int64_t N, int64_t P, int64_t Dt, void* workspace, int64_t workspace_bytes, int* best, float* query, int* info, float* v_out, double* mean_out, double* sim_out);
 int owl_query_bank_fill(void* stream, const float* query, const int* row_ptr, const int* members, float* bank, int64_t N, int64_t nq, int64_t Dt);
 
+/* ---- open-vocabulary class head, forward only (still ABI 8: additive; csrc/open_vocab.hip, models.OwlViT.detect / detect_text) ----------------------
+ * HF's OwlViTClassPredictionHead over query banks that differ per image (text prompts, or an image exemplar's embedding).  Inference only: there is
+ * no backward, nothing is trained through it, and the fine-tuning head's kernels are untouched.  For image b, patch p, query q:
+ *     e^_p     = e_p / (|e_p| + 1e-6)              e  f32 [B P, Dt]: the class head's dense0 output
+ *     q^_{b,q} = Q_{b,q} / (|Q_{b,q}| + 1e-6)      queries f32 [nbanks, Q, Dt], nbanks = B (a bank per image) or 1 (one bank for the batch).  HF's epsilon
+ *                                                  placement, not owl_query_normalize's; an all-zero row (HF's padded query) stays all-zero, never NaN
+ *     shift_p  = w_shift . f_p + b_shift           feats bf16 [B P, D]: post_post_layernorm's output; w_shift / w_scale f32 [D]; b_shift / b_scale f32 [1]
+ *     scale_p  = elu(w_scale . f_p + b_scale) + 1  on the DEVICE
+ *     logits[b, p, q] = (e^_p . q^_{b,q} + shift_p) * scale_p, in this order; finfo(f32).min (-FLT_MAX) where mask[b, q] == 0
+ *     scores[b, p, q] = 1 / (1 + exp(-logit)), exactly 0 where masked (scores may be NULL)
+ *   mask u8 [nmasks, Q], nmasks = B or 1, nonzero = valid (HF's query_mask); NULL = every query valid.  logits / scores f32 [B, P, Q].
+ *   rowstats f32 [B P, 2]: caller's scratch; a pre-pass writes (shift_p, scale_p) there once per row -- f32 FMAs over the widened bf16 features in one
+ *   fixed order -- and every block of 32 queries reads those bits.  The cosine term runs on v_mfma_f32_32x32x2f32 with a 32-query table in LDS
+ *   ([32][Dt + 4] f32), normalised while it is loaded; 32-row tiles never straddle two images.
+ *   1 <= Q <= 4096, Dt % 64 == 0 (Dt <= 1024: the table must fit LDS), D % 8 == 0, 1 <= P <= 8192, 1 <= B P < 2^31; e, queries, feats, w_shift, w_scale
+ *   16-byte aligned.  Two launches, no atomics, nothing allocated, no host sync; two runs give equal bits, and an image's block or a query's column
+ *   carries the same bits wherever it stands in the batch or the bank.                                                                               */
+int owl_class_logits_fwd(void* stream, const float* e, const float* queries, const void* feats_bf16, const float* w_shift, const float* b_shift, const float* w_scale, const float* b_scale, const unsigned char* mask, float* rowstats, float* logits, float* scores, int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t nmasks, int64_t Dt, int64_t D);
+
 /* ---- utilities ------------------------------------------------------------------------------------ */
 int owl_cast_f32_bf16(void* stream, const float* in, void* out, int64_t n);
 int owl_transpose_bf16(void* stream, const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t R, int64_t C);

@@ -240,6 +240,9 @@ class OwlViT(nn.Module):
         # a frozen tensor empties it.
         self.prefix_cache = None
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate_prefix())
+        # HF's class_head.logit_shift / logit_scale for zero-shot inference (detect): frozen device buffers outside flat_param, the parameter tree and
+        # every state dict (plain attributes, as box_bias is); None until set_logit_head
+        self.logit_head = None
 
     # -- module-tree plumbing -----------------------------------------------------------------------
     def _attach(self, dotted: str, p: nn.Parameter):
@@ -934,8 +937,124 @@ class OwlViT(nn.Module):
         self._bf16_current = False          # a raw-pointer write the bucket's version counter does not see: the next forward recasts the bf16 copy
         return dict(box_indices=[h[0] for h in host], n_selected=[h[2] for h in host], fallback=[bool(h[1] & 1) for h in host], slots=table)
 
+    # -- zero-shot inference: HF's class head over per-image text / image queries ---------------------------------------------
+    def set_logit_head(self, head):
+        """head: weights.hf_logit_head(sd) -- {"logit_shift.weight" [D], "logit_shift.bias" [], "logit_scale.weight" [D], "logit_scale.bias" []} (arrays
+        or tensors).  They become frozen f32 device buffers in `model.logit_head`, outside flat_param, parameters() and state_dict(): nothing trains
+        through them and no checkpoint changes.  None removes them.  ValueError names a tensor of the wrong size, KeyError a missing one."""
+        if head is None:
+            self.logit_head = None
+            return self
+        D, out = self.cfg.hidden, {}
+        for k in W.LOGIT_HEAD_KEYS:
+            if k not in head:
+                raise KeyError(f"set_logit_head: `{k}` is missing (weights.hf_logit_head builds the four tensors)")
+            t = torch.as_tensor(np.asarray(head[k].detach().cpu() if torch.is_tensor(head[k]) else head[k]), dtype=torch.float32).reshape(-1)
+            want = D if k.endswith("weight") else 1
+            if t.numel() != want:
+                raise ValueError(f"set_logit_head: `{k}` must have {want} element(s) for hidden size {D}, got {t.numel()}")
+            out[k] = t.contiguous().to(self.device_)
+        self.logit_head = out
+        return self
 
-EXEMPLAR_CHUNK = 32          # images per forward of embed_image_query
+    @torch.no_grad()
+    def detect(self, pixel_values, query_embeds, query_mask=None, return_scores=False):
+        """Zero-shot detection, HF `OwlViTForObjectDetection` logits: -> (pred_boxes [B, P, 4], logits [B, P, Q]) and, with return_scores=True,
+        scores = sigmoid(logits) [B, P, Q] (exactly 0 where masked).  pred_boxes are CORNERS (x0, y0, x1, y1), as everywhere in this project; HF's
+        `pred_boxes` are (cx, cy, w, h).
+
+        query_embeds: f32 [B, Q, Dt] (a bank per image) or [Q, Dt] (one bank shared by the batch, read where it lies: no copy per image), on any device;
+        1 <= Q <= 4096.  query_mask: [B, Q] or [Q], bool / integer, nonzero = valid -- HF's `query_mask`; masked logits are finfo(f32).min, as HF
+        writes them.  Queries are normalised HF's way, q / (|q| + 1e-6); unit text rows are therefore normalised a second time, as in HF.
+
+        Image-guided detection needs no other entry: `model.detect(img, model.embed_image_query(ex, boxes)[0][None])` is HF's
+        `image_guided_detection` for one exemplar.  HF's post-processing is `PostProcess(confidence_threshold=t, iou_threshold=1.0)(pred_boxes, scores)`
+        (the class is the arg-max query; an IoU threshold of 1 keeps everything, HF's `post_process_object_detection` has no NMS).
+
+        Needs `set_logit_head` (RuntimeError otherwise).  Inference only: nothing is trained through this head.  Runs the plain eval forward on the EVAL
+        workspace behind a deferred optimizer tail (a pending training backward is not disturbed), in chunks of at most 32 images; the frozen-prefix
+        cache is neither read nor written; `forward` and its outputs are untouched.  No host sync."""
+        if self.logit_head is None:
+            raise RuntimeError("detect: no logit head -- call model.set_logit_head(weights.hf_logit_head(hf_state_dict)) or load_model(..., logit_head=)")
+        B, Q, shared = check_detect_args(self.cfg, pixel_values, query_embeds, query_mask)
+        cfg, dev, P = self.cfg, self.device_, self.cfg.patches
+        qe = torch.as_tensor(query_embeds).to(dev).contiguous()
+        qm = None
+        if query_mask is not None:
+            qm = (torch.as_tensor(query_mask).to(dev) != 0).to(torch.uint8).contiguous()
+        lh = self.logit_head
+        self._wait_params()
+        boxes = torch.empty(B, P, 4, dtype=torch.float32, device=dev)
+        logits = torch.empty(B, P, Q, dtype=torch.float32, device=dev)
+        scores = torch.empty(B, P, Q, dtype=torch.float32, device=dev) if return_scores else None
+        keep = self.max_cached_batch_sizes          # (as _embed_image_query: no size is evicted by this call)
+        self.max_cached_batch_sizes = max(1, int(keep)) + 2
+        try:
+            for a in range(0, B, EXEMPLAR_CHUNK):
+                nb = min(EXEMPLAR_CHUNK, B - a)
+                pb, _ = self._forward_impl(pixel_values[a:a + nb], save=False)
+                ws = self._workspace(nb, train=False)
+                if "logit_rowstats" not in ws:
+                    ws["logit_rowstats"] = torch.zeros(nb * P, 2, dtype=torch.float32, device=dev)
+                ops.class_logits(ws["e"], qe if shared else qe[a:a + nb], ws["feats"], lh["logit_shift.weight"], lh["logit_shift.bias"],
+                                 lh["logit_scale.weight"], lh["logit_scale.bias"], nb, P, mask=None if qm is None else (qm if qm.dim() == 1 else qm[a:a + nb]),
+                                 rowstats=ws["logit_rowstats"], logits=logits[a:a + nb], scores=scores[a:a + nb] if return_scores else False)
+                boxes[a:a + nb].copy_(pb)
+        finally:
+            self.max_cached_batch_sizes = keep
+        return (boxes, logits, scores) if return_scores else (boxes, logits)
+
+    @torch.no_grad()
+    def detect_text(self, pixel_values, input_ids, text_tower, return_scores=False, shared=None):
+        """`detect` on tokenised prompts, HF's `OwlViTForObjectDetection.forward`: input_ids [B Q, S] (HF's layout) or [B, Q, S], Q prompts per image that
+        may differ per image, padded queries all-zero ids; or [Q, S] for one list shared by the batch.  A 2-D input whose row count is a multiple of B
+        is read as [B Q, S] unless shared=True.  The embeddings are `text_tower.encode(ids)` (text.TextTower: the unit rows HF feeds its head), the
+        mask is ids[..., 0] > 0 as in HF.  -> detect's result."""
+        B = int(pixel_values.shape[0])
+        ids = torch.as_tensor(np.asarray(input_ids) if not torch.is_tensor(input_ids) else input_ids)
+        if ids.dim() == 3:
+            if ids.shape[0] != B:
+                raise ValueError(f"detect_text: input_ids must be [{B}, Q, S], [{B} Q, S] or [Q, S], got {tuple(ids.shape)}")
+            shape = (B, int(ids.shape[1]))
+        elif ids.dim() == 2:
+            if shared is None:
+                shared = ids.shape[0] % B != 0
+            if not shared and ids.shape[0] % B:
+                raise ValueError(f"detect_text: input_ids [{ids.shape[0]}, S] is not [{B} Q, S] for a batch of {B} images")
+            shape = (int(ids.shape[0]),) if shared else (B, int(ids.shape[0]) // B)
+        else:
+            raise ValueError(f"detect_text: input_ids must be [{B}, Q, S], [{B} Q, S] or [Q, S], got {tuple(ids.shape)}")
+        flat = ids.reshape(-1, ids.shape[-1])
+        embeds = text_tower.encode(flat).reshape(*shape, -1)
+        mask = (flat[:, 0] > 0).reshape(*shape)
+        return self.detect(pixel_values, embeds, mask, return_scores=return_scores)
+
+
+def check_detect_args(cfg, pixel_values, query_embeds, query_mask=None):
+    """Host-side validation of OwlViT.detect's arguments (shapes and dtypes only: no device is touched) -> (B, Q, shared bank?).  ValueError names
+    the expected shape."""
+    if not hasattr(pixel_values, "shape") or len(pixel_values.shape) != 4 or tuple(pixel_values.shape[1:]) != (3, cfg.image_size, cfg.image_size) \
+            or pixel_values.shape[0] < 1:
+        raise ValueError(f"detect: pixel_values must be [B, 3, {cfg.image_size}, {cfg.image_size}] with B >= 1, got {tuple(getattr(pixel_values, 'shape', ()))}")
+    B, Dt = int(pixel_values.shape[0]), cfg.text_dim
+    qe = torch.as_tensor(query_embeds)
+    if qe.dim() not in (2, 3) or qe.shape[-1] != Dt or (qe.dim() == 3 and qe.shape[0] != B):
+        raise ValueError(f"detect: query_embeds must be [{B}, Q, {Dt}] or [Q, {Dt}], got {tuple(qe.shape)}")
+    if qe.dtype != torch.float32:
+        raise ValueError(f"detect: query_embeds must be float32 [{B}, Q, {Dt}] or [Q, {Dt}], got {qe.dtype}")
+    Q = int(qe.shape[-2])
+    if not 1 <= Q <= ops.CLASS_LOGITS_MAX_QUERIES:
+        raise ValueError(f"detect: query_embeds must be [{B}, Q, {Dt}] or [Q, {Dt}] with 1 <= Q <= {ops.CLASS_LOGITS_MAX_QUERIES}, got Q = {Q}")
+    if query_mask is not None:
+        qm = torch.as_tensor(query_mask)
+        if tuple(qm.shape) not in ((B, Q), (Q,)):
+            raise ValueError(f"detect: query_mask must be [{B}, {Q}] or [{Q}], got {tuple(qm.shape)}")
+        if qm.dtype.is_floating_point or qm.dtype.is_complex:
+            raise ValueError(f"detect: query_mask must be bool or integer [{B}, {Q}] or [{Q}] (nonzero = valid), got {qm.dtype}")
+    return B, Q, qe.dim() == 2
+
+
+EXEMPLAR_CHUNK = 32          # images per forward of embed_image_query and detect
 
 
 def exemplar_slots(class_ids, n_classes):
@@ -979,7 +1098,7 @@ def check_exemplars(class_ids, query_boxes, n_images, n_classes):
 
 
 def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed: int = 1234, state=None, *,
-               prompt_ids=None, text_state=None, vocab=None, merges=None, trainable=None, image_size=None, exemplars=None):
+               prompt_ids=None, text_state=None, vocab=None, merges=None, trainable=None, image_size=None, exemplars=None, logit_head=None):
     """ref src/models.py:149-191.  The reference downloads `google/owlvit-base-patch32` and runs the
     CLIP text tower once to initialise the query bank; neither box has network access, so weights
     come from `state` (name -> array, reference parameter names) or, by default, the deterministic
@@ -1006,7 +1125,10 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
 
     `exemplars` (None = nothing new runs or is allocated): `(pixel_values, class_ids[, query_boxes])`, annotated example images at the model's input size --
     the image prior for classes a short prompt does not describe.  Applied after construction, hence after the text initialisation when `prompt_ids=` /
-    `vocab=` is given too (OwlViT.set_queries_from_exemplars): classes with exemplars take the image prior, the others keep the text (or random) one."""
+    `vocab=` is given too (OwlViT.set_queries_from_exemplars): classes with exemplars take the image prior, the others keep the text (or random) one.
+
+    `logit_head` (None = none is set): weights.hf_logit_head(sd), HF's `class_head.logit_shift / logit_scale` -- what zero-shot inference
+    (OwlViT.detect / detect_text) needs beside the vision path.  Frozen buffers outside the parameters: see OwlViT.set_logit_head."""
     n_classes = len(labelmap)
     cfg = get_config(arch, n_classes=n_classes)
     g0 = table_grid(np.asarray(state[_POS]).shape[0]) if (state is not None and _POS in state) else cfg.grid
@@ -1042,4 +1164,6 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
         if not 2 <= len(exemplars) <= 3:
             raise ValueError("load_model: exemplars= is (pixel_values, class_ids) or (pixel_values, class_ids, query_boxes)")
         model.set_queries_from_exemplars(*exemplars)
+    if logit_head is not None:
+        model.set_logit_head(logit_head)
     return model

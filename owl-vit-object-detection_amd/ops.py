@@ -176,6 +176,54 @@ def class_sims_wide(e, qhat_wide, sims, argmax, inv_norm, rows, Dt, C):
     _lib.call("owl_class_sims_wide_fwd", stream(), e, qhat_wide, sims, argmax, inv_norm, rows, Dt, C)
 
 
+CLASS_LOGITS_MAX_QUERIES = 4096     # ceiling of class_logits (csrc/open_vocab.hip OV_MAX_QUERIES)
+
+
+def class_logits(e, queries, feats, w_shift, b_shift, w_scale, b_scale, B, P, mask=None, rowstats=None, logits=None, scores=False):
+    """HF's OwlViTClassPredictionHead over per-image query banks (include/owl_hip.h owl_class_logits_fwd; inference only, no backward):
+    logits[b, p, q] = (e^_p . q^_{b,q} + shift_p) * scale_p with HF's q / (|q| + 1e-6), finfo(f32).min where mask == 0.
+    e f32 [>= B P, Dt]; queries f32 [B, Q, Dt] or [Q, Dt] (one bank for the batch, read where it lies); feats bf16 [>= B P, D]; w_shift / w_scale f32 [D];
+    b_shift / b_scale f32 device tensors of one element; mask uint8 [B, Q] or [Q] (nonzero = valid) or None.  rowstats (f32 [>= B P, 2] scratch: (shift,
+    scale) per row afterwards) and logits (f32 [B, P, Q]) are allocated when not given; scores: False, True (allocate) or an f32 [B, P, Q] tensor.
+    -> (logits, scores or None, rowstats).  No host sync."""
+    _chk(e, torch.float32, "e"); _chk(queries, torch.float32, "queries"); _chk(feats, torch.bfloat16, "feats")
+    _chk(w_shift, torch.float32, "w_shift"); _chk(b_shift, torch.float32, "b_shift"); _chk(w_scale, torch.float32, "w_scale"); _chk(b_scale, torch.float32, "b_scale")
+    _chk(mask, torch.uint8, "mask"); _chk(rowstats, torch.float32, "rowstats"); _chk(logits, torch.float32, "logits")
+    B, P = int(B), int(P)
+    if queries.dim() not in (2, 3) or (queries.dim() == 3 and queries.shape[0] != B):
+        raise ValueError(f"class_logits: queries must be [{B}, Q, Dt] or [Q, Dt], got {tuple(queries.shape)}")
+    Q, Dt = int(queries.shape[-2]), int(queries.shape[-1])
+    D = int(w_shift.numel())
+    if e.dim() != 2 or e.shape[1] != Dt or e.shape[0] < B * P:
+        raise ValueError(f"class_logits: e must be [>= {B * P}, {Dt}], got {tuple(e.shape)}")
+    if feats.dim() != 2 or feats.shape[1] != D or feats.shape[0] < B * P or w_scale.numel() != D or b_shift.numel() != 1 or b_scale.numel() != 1:
+        raise ValueError(f"class_logits: feats must be [>= {B * P}, D], w_shift / w_scale [D], b_shift / b_scale one element each (D = {D}, feats {tuple(feats.shape)})")
+    if not 1 <= Q <= CLASS_LOGITS_MAX_QUERIES:
+        raise ValueError(f"class_logits: 1 <= Q <= {CLASS_LOGITS_MAX_QUERIES} queries per image, got {Q}")
+    if mask is not None and tuple(mask.shape) not in ((B, Q), (Q,)):
+        raise ValueError(f"class_logits: mask must be [{B}, {Q}] or [{Q}], got {tuple(mask.shape)}")
+    dev = e.device
+    if rowstats is None:
+        rowstats = torch.empty(B * P, 2, dtype=torch.float32, device=dev)
+    elif rowstats.numel() < 2 * B * P:
+        raise ValueError(f"class_logits: rowstats must hold [{B * P}, 2] floats")
+    if logits is None:
+        logits = torch.empty(B, P, Q, dtype=torch.float32, device=dev)
+    elif tuple(logits.shape) != (B, P, Q):
+        raise ValueError(f"class_logits: logits must be [{B}, {P}, {Q}], got {tuple(logits.shape)}")
+    if scores is True:
+        scores = torch.empty(B, P, Q, dtype=torch.float32, device=dev)
+    elif scores is False:
+        scores = None
+    else:
+        _chk(scores, torch.float32, "scores")
+        if tuple(scores.shape) != (B, P, Q):
+            raise ValueError(f"class_logits: scores must be [{B}, {P}, {Q}], got {tuple(scores.shape)}")
+    _lib.call("owl_class_logits_fwd", stream(), e, queries, feats, w_shift, b_shift, w_scale, b_scale, mask, rowstats, logits, scores,
+              B, P, Q, B if queries.dim() == 3 else 1, (B if mask.dim() == 2 else 1) if mask is not None else 1, Dt, D)
+    return logits, scores, rowstats
+
+
 def box_final(h, w2, b2, box_bias, boxes, sig, rows, P, D):
     _chk(h, torch.bfloat16, "h"); _chk(w2, torch.float32, "w2")
     _lib.call("owl_box_final_fwd", stream(), h, w2, b2, box_bias, boxes, sig, rows, P, D)

@@ -289,6 +289,30 @@ def from_hf_state_dict(sd, queries=None) -> "OrderedDict[str, np.ndarray]":
     return out
 
 
+LOGIT_HEAD_KEYS = ("logit_shift.weight", "logit_shift.bias", "logit_scale.weight", "logit_scale.bias")
+
+
+def hf_logit_head(sd) -> "OrderedDict[str, np.ndarray]":
+    """The four tensors of HF's `class_head.logit_shift / logit_scale` (two Linear(D, 1)) out of an `OwlViTForObjectDetection.state_dict()`, which
+    `from_hf_state_dict` drops as the reference does: {"logit_shift.weight" [D], "logit_shift.bias" [], "logit_scale.weight" [D], "logit_scale.bias" []},
+    float32 ndarrays.  They are NOT parameters of the model (param_shapes, the flat bucket and every state dict stay as they are): hand them to
+    `OwlViT.set_logit_head` / `load_model(..., logit_head=)` for zero-shot inference (`detect`).  Values may be torch tensors or arrays; a missing tensor
+    raises KeyError naming it."""
+    out = OrderedDict()
+    for k in LOGIT_HEAD_KEYS:
+        key = "class_head." + k
+        if key not in sd:
+            raise KeyError(f"hf_logit_head: `{key}` is not in the state dict")
+        v = sd[key]
+        if hasattr(v, "detach"):
+            v = v.detach().to("cpu").float().numpy()
+        v = np.asarray(v, dtype=np.float32)
+        out[k] = np.ascontiguousarray(v.reshape(-1)) if k.endswith("weight") else v.reshape(()).copy()          # (ascontiguousarray would make a scalar 1-d)
+    if out["logit_shift.weight"].shape != out["logit_scale.weight"].shape:
+        raise ValueError("hf_logit_head: logit_shift.weight and logit_scale.weight differ in size")
+    return out
+
+
 def patch_weight_gather_layout(w, patch_size: int):
     """The patch-embedding weight [D, 3, ps, ps] (HF5:282-288) in the K order of the im2row-free loader (csrc/gemm_pp2.hip stage_A, include/owl_hip.h
     owl_patch_embed_bf16): [D, Kg] with k = (c * ps + ky) * psp + pos, psp = the power of two >= ps, Kg = 3 * ps * psp rounded up to 64.  Position `pos` of a
