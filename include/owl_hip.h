@@ -221,6 +221,17 @@ int owl_bicubic_coeffs_box(int64_t in_size, double in0, double in1, int64_t out_
  * [n_out,3,out_h,out_w] f32 | bf16.  max_rows = max n_rows.  The CALLER guarantees 0 <= b < n_out and that the cells of every output image lie inside it
  * and cover it exactly (the descriptors live in device memory: preprocess.check_tile_cover is the host check).                                          */
 int owl_preprocess_u8_tiles(void* stream, const void* desc, int64_t n_tiles, int64_t max_rows, unsigned char* tmp, const float* lut, void* out, int out_bf16, int64_t n_out, int64_t out_h, int64_t out_w);
+/* Colour jitter in the tile resampler (still ABI 8: additive; csrc/color_jitter.hip).  owl_preprocess_u8_tiles_color = owl_preprocess_u8_tiles with Pillow's
+ * ImageEnhance.Brightness / Contrast / Color applied to every tile's resized cell, bit for bit, between the resize and the table:
+ * color = n_tiles x 4 f32 in DEVICE memory (16-byte aligned), per tile {fb, fc, fs, order}: factors >= 0 and order 0..5 (stored as a float) indexing
+ * itertools.permutations("bcs") in lexicographic order = the sequence the three ops are applied in.  Brightness(f) = blend(0, c, f), Color(f) = blend(L, c, f),
+ * Contrast(f) = blend(m, c, f); L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16; m = (2 sum L + n) / (2 n) over the n = cw x ch pixels of the cell as they
+ * are when contrast is reached; blend(a, b, f) = clip-then-truncate of f32(a) + fl32(f * f32(b - a)) (two roundings).  A factor of exactly 1 is the identity;
+ * the all-ones array gives the bits of owl_preprocess_u8_tiles.  Grayscale = fs 0.  workspace: DEVICE memory (4-byte aligned) of at least the
+ * owl_preprocess_color_workspace_bytes (HOST function; `bytes` a host pointer) of the same n_tiles / out_h / out_w; it need not be initialised.  `out` is
+ * used as the u8 canvas between the passes.  Same caller guarantees as owl_preprocess_u8_tiles; the CALLER validates `color` (preprocess.check_color).     */
+int owl_preprocess_color_workspace_bytes(int64_t n_tiles, int64_t out_h, int64_t out_w, int64_t* bytes);
+int owl_preprocess_u8_tiles_color(void* stream, const void* desc, const float* color, int64_t n_tiles, int64_t max_rows, unsigned char* tmp, void* workspace, int64_t workspace_bytes, const float* lut, void* out, int out_bf16, int64_t n_out, int64_t out_h, int64_t out_w);
 /* images that already have the model's size (ABI 6): src u8 [n,H,W,3] (src_chw = 0) or [n,3,H,W] (src_chw = 1) -> lut -> out [n,3,H,W] f32 | bf16.  Pillow's resize
  * to the size an image already has is a copy, so this IS the reference pipeline for such images, bit for bit.  H*W % 4 == 0; src 4-byte, out 16-byte aligned.       */
 int owl_normalize_u8(void* stream, const unsigned char* src, int src_chw, const float* lut, void* out, int out_bf16, int64_t n_images, int64_t H, int64_t W);

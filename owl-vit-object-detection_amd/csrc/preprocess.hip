@@ -6,14 +6,7 @@
 // Everything after the resize is a function of one u8 level per channel, so rescale+normalize is a [3][256] f32 table
 // built by the caller with the reference's own float arithmetic -> the whole pipeline is bit-exact.  HBM-bound byte
 // work (no MFMA): per image it reads H*W*3 B, writes/reads the H x S u8 intermediate, writes 3*S*S*(4|2) B.
-#include "common.h"
-
-#define PIL_PRECISION_BITS 22
-
-__device__ __forceinline__ unsigned char pil_clip8(int v) {
-    v >>= PIL_PRECISION_BITS;
-    return (unsigned char)min(255, max(0, v));
-}
+#include "preprocess_tiles.h"
 
 // ---- one launch pair for a ragged batch (a per-image form was launch-bound -- 2 launches per image, 0.44 against 0.22 ms for 32 images -- and had no caller: removed in round 4) ----
 // desc[i] = {src, H, W, bounds_x, kk_x, ksize_x, bounds_y, kk_y, ksize_y, tmp byte offset} as 10 int64 (device memory)
@@ -87,15 +80,7 @@ OWL_API int owl_preprocess_u8_batch(void* stream, const void* desc, int64_t n_im
 // edges, taps clipped to the image), the flip and the cell origin in the store address, so every source pixel is still interpolated once, Pillow-exact:
 // Image.resize((cw, ch), BICUBIC, box=...) [.transpose(FLIP_LEFT_RIGHT)] pasted at (x0, y0).  Like Pillow (Resample.c ImagingResample: ybox_first / ybox_last)
 // the horizontal pass runs only over the source rows [y_first, y_first + n_rows) that the vertical taps read; the intermediate is u8 [n_rows, cw, 3].
-// desc[i] = 18 int64 (device memory); the caller guarantees that the tiles of an output image cover it exactly (preprocess.py checks it on the host).
-struct TileDesc { const unsigned char* src; long long H, W; const int* bx; const int* kx; long long ksx; const int* by; const int* ky; long long ksy;
-                  long long y_first, n_rows, tmp_off, b, x0, y0, cw, ch, flip; };
-
-// A thread produces TILE_ROWS vertically adjacent pixels: a quarter of the workgroups (most of a mosaic's grid lies outside the small cells and only leaves
-// again), and in the horizontal pass one read of a column's weights serves four source rows.  Integer sums: the grouping cannot change a bit.
-// (Tried: gridDim.x workgroups per tile walking the tile's 256 x TILE_ROWS units, so that no workgroup starts without work -- slower at g = 1 and 2, equal
-// at g = 3, profiles/augment.md: the passes are bound by their byte loads per tap, not by the empty workgroups.)
-#define TILE_ROWS 4
+// struct TileDesc and TILE_ROWS (the rows a thread takes): preprocess_tiles.h, shared with the colour path (color_jitter.hip).
 
 __global__ __launch_bounds__(256) void pp_tile_h_kernel(const TileDesc* __restrict__ desc, unsigned char* __restrict__ tmp_base) {
     const TileDesc d = desc[blockIdx.z];
@@ -174,6 +159,13 @@ OWL_API int owl_preprocess_u8_tiles(void* stream, const void* desc, int64_t n_ti
         hipLaunchKernelGGL((pp_tile_v_kernel<true>), dim3(gx, gy, (unsigned)n_tiles), dim3(256), 0, s, (const TileDesc*)desc, tmp, out, lut, (int)out_h, (int)out_w);
     else
         hipLaunchKernelGGL((pp_tile_v_kernel<false>), dim3(gx, gy, (unsigned)n_tiles), dim3(256), 0, s, (const TileDesc*)desc, tmp, out, lut, (int)out_h, (int)out_w);
+    OWL_LAUNCH_CHECK();
+    return 0;
+}
+
+// The horizontal pass alone, for owl_preprocess_u8_tiles_color (color_jitter.hip), whose vertical pass differs.  Sizes checked by the caller.
+int pp_tile_h_launch(hipStream_t s, const TileDesc* desc, int64_t n_tiles, int64_t max_rows, unsigned char* tmp, int64_t out_w) {
+    hipLaunchKernelGGL(pp_tile_h_kernel, dim3((unsigned)((out_w + 255) / 256), (unsigned)((max_rows + TILE_ROWS - 1) / TILE_ROWS), (unsigned)n_tiles), dim3(256), 0, s, desc, tmp);
     OWL_LAUNCH_CHECK();
     return 0;
 }

@@ -40,6 +40,7 @@ class DeviceImageProcessor:
         self.lut = torch.from_numpy(normalize_lut(image_mean, image_std, rescale_factor)).to(self.device)
         self._tables = {}
         self._tmp = None
+        self._ws = None                      # partial sums of the colour path (owl_preprocess_color_workspace_bytes)
 
     def _axis_tables(self, in_size: int):
         key = in_size
@@ -85,30 +86,44 @@ class DeviceImageProcessor:
         self._keep = (imgs, desc_d)          # keep the sources alive until the stream has consumed them
         return {"pixel_values": out}
 
-    def run_tiles(self, desc_d: torch.Tensor, n_tiles: int, max_rows: int, tmp_bytes: int, n_out: int) -> torch.Tensor:
+    def run_tiles(self, desc_d: torch.Tensor, n_tiles: int, max_rows: int, tmp_bytes: int, n_out: int, color=None) -> torch.Tensor:
         """Launch owl_preprocess_u8_tiles on the current stream for descriptors that are already on the device with absolute addresses (`build_tile_tables` +
-        `resolve_tile_descs`) and whose cover the caller has checked (`check_tile_cover`) -> [n_out,3,S,S] self.dtype."""
+        `resolve_tile_descs`) and whose cover the caller has checked (`check_tile_cover`) -> [n_out,3,S,S] self.dtype.  `color`: a DEVICE f32 [n_tiles,4] array of
+        (fb, fc, fs, order) rows the caller has checked (`check_color`) -> owl_preprocess_u8_tiles_color instead; None: the plain launch pair, as ever."""
         if self._tmp is None or self._tmp.numel() < tmp_bytes:
             self._tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=self.device)
         out = torch.empty(n_out, 3, self.size, self.size, dtype=self.dtype, device=self.device)
-        _lib.call("owl_preprocess_u8_tiles", ops.stream(), desc_d, n_tiles, max_rows, self._tmp, self.lut, out,
+        if color is None:
+            _lib.call("owl_preprocess_u8_tiles", ops.stream(), desc_d, n_tiles, max_rows, self._tmp, self.lut, out,
+                      1 if self.dtype == torch.bfloat16 else 0, n_out, self.size, self.size)
+            return out
+        if not (torch.is_tensor(color) and color.is_cuda and color.dtype == torch.float32 and tuple(color.shape) == (n_tiles, 4) and color.is_contiguous()):
+            raise ValueError(f"run_tiles: color must be a contiguous device float32 [{n_tiles},4] tensor")
+        need = color_workspace_bytes(n_tiles, self.size)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        _lib.call("owl_preprocess_u8_tiles_color", ops.stream(), desc_d, color, n_tiles, max_rows, self._tmp, self._ws, self._ws.numel(), self.lut, out,
                   1 if self.dtype == torch.bfloat16 else 0, n_out, self.size, self.size)
         return out
 
-    def tiles(self, images, tiles, n_out: int) -> torch.Tensor:
+    def tiles(self, images, tiles, n_out: int, color=None) -> torch.Tensor:
         """The augmenting form of __call__: every `Tile` resamples a source box of `images[tile.src]` into a cell of output image `tile.b`, flipped or not --
         Pillow's `resize((cw, ch), BICUBIC, box=...)`, `transpose(FLIP_LEFT_RIGHT)` and `paste`, bit for bit, in one launch pair.  Raises ValueError unless
-        the cells of every output image cover it exactly."""
+        the cells of every output image cover it exactly.  `color` (host, [n_tiles,4] rows of (fb, fc, fs, order): `ColorJitter.sample`, `check_color`) puts
+        Pillow's `ImageEnhance.Brightness / Contrast / Color` on each resized cell, in the row's order, between the resize and the table."""
         imgs = [self._to_device(im) for im in images]
         shapes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
         tiles = list(tiles)
         check_tile_cover(tiles, n_out, self.size, shapes)
+        color_d = None
+        if color is not None:
+            color_d = torch.from_numpy(check_color(color, len(tiles))).to(self.device, non_blocking=True)
         desc, arena, tmp_bytes, max_rows = build_tile_tables(shapes, tiles)
         arena_d = torch.from_numpy(arena).to(self.device, non_blocking=True)
         resolve_tile_descs(desc, [im.data_ptr() for im in imgs], arena_d.data_ptr())
         desc_d = torch.from_numpy(desc).to(self.device, non_blocking=True)
-        out = self.run_tiles(desc_d, len(tiles), max_rows, tmp_bytes, n_out)
-        self._keep = (imgs, arena_d, desc_d)          # keep the sources and tables alive until the stream has consumed them
+        out = self.run_tiles(desc_d, len(tiles), max_rows, tmp_bytes, n_out, color=color_d)
+        self._keep = (imgs, arena_d, desc_d, color_d)          # keep the sources and tables alive until the stream has consumed them
         return out
 
     def normalize_sized(self, src_u8: torch.Tensor, chw: bool) -> torch.Tensor:
@@ -267,6 +282,89 @@ def transform_boxes(boxes_xywh, labels, crop, flip, cell, size, min_visibility=0
     return res + (keep,) if return_mask else res
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The photometric half: brightness, contrast, saturation and random grayscale, per TILE, on the resized cell (csrc/color_jitter.hip) -- Pillow's
+# `ImageEnhance.Brightness / Contrast / Color(cell).enhance(f)`, bit for bit (what torchvision's PIL path calls for `adjust_brightness / contrast /
+# saturation`).  No hue: Pillow's RGB <-> HSV round trip is not pinned.  The host only draws the factors.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+COLOR_ORDERS = ("bcs", "bsc", "cbs", "csb", "sbc", "scb")     # itertools.permutations("bcs"), lexicographic: what `order` 0..5 of a colour row indexes
+
+
+def check_color(color, n_tiles: int) -> np.ndarray:
+    """-> `color` as a contiguous float32 [n_tiles,4] array of (fb, fc, fs, order) rows; raises ValueError unless every value is finite, every factor >= 0
+    and every order one of 0..5."""
+    try:
+        c = np.ascontiguousarray(np.asarray(color, dtype=np.float32))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"color: expected a float [n_tiles,4] array ({e})") from None
+    if c.shape != (int(n_tiles), 4):
+        raise ValueError(f"color: expected shape ({int(n_tiles)}, 4) = a (brightness, contrast, saturation, order) row per tile, got {c.shape}")
+    if not np.isfinite(c).all():
+        raise ValueError("color: non-finite value")
+    if (c[:, :3] < 0).any():
+        raise ValueError("color: factors must be >= 0")
+    if not np.isin(c[:, 3], np.arange(6, dtype=np.float32)).all():
+        raise ValueError("color: order must be one of 0..5 (itertools.permutations('bcs'))")
+    return c
+
+
+def color_workspace_bytes(n_tiles: int, size: int) -> int:
+    """Bytes of device workspace owl_preprocess_u8_tiles_color needs for `n_tiles` tiles of size x size canvases (asked of the library)."""
+    got = np.zeros(1, dtype=np.int64)
+    _lib.call("owl_preprocess_color_workspace_bytes", int(n_tiles), int(size), int(size), got.ctypes.data)
+    return int(got[0])
+
+
+class ColorJitter:
+    """Deterministic host-side sampler of per-tile colour factors: `TrainAugment(size, color=ColorJitter(0.4, 0.4, 0.4, gray=0.1))`.
+
+    `brightness`, `contrast`, `saturation`: a strength x >= 0 = a factor uniform in [max(0, 1 - x), 1 + x] (torchvision's convention), or an explicit
+    (lo, hi) range with 0 <= lo <= hi.  `gray`: the probability that a tile's saturation factor becomes 0 (Pillow's `convert("L")` in all three channels).
+    `p`: the probability that a tile is jittered at all; the others get the identity row.  The three ops are applied in a random one of their six orders.
+
+    `sample(n_tiles, key)` draws from `numpy.random.default_rng((*key, 1))`, key = (seed, rank, epoch, index) -- a stream of its own beside
+    `TrainAugment.sample`'s, so turning colour on changes no tile, box or label.  The six arrays (brightness, contrast, saturation, order, gray, p) are
+    ALWAYS drawn, each for all tiles, in that sequence, whatever the strengths: changing one strength never shifts another op's draws."""
+
+    def __init__(self, brightness=0.0, contrast=0.0, saturation=0.0, gray=0.0, p=1.0):
+        self.brightness = self._range("brightness", brightness)
+        self.contrast = self._range("contrast", contrast)
+        self.saturation = self._range("saturation", saturation)
+        self.gray, self.p = float(gray), float(p)
+        if not (0.0 <= self.gray <= 1.0 and 0.0 <= self.p <= 1.0):
+            raise ValueError("ColorJitter: gray and p are probabilities in [0, 1]")
+
+    @staticmethod
+    def _range(name, x):
+        if isinstance(x, (tuple, list)):
+            if len(x) != 2:
+                raise ValueError(f"ColorJitter: {name} must be a strength or a (lo, hi) range")
+            lo, hi = float(x[0]), float(x[1])
+        else:
+            x = float(x)
+            if not x >= 0.0:
+                raise ValueError(f"ColorJitter: {name} strength must be >= 0")
+            lo, hi = max(0.0, 1.0 - x), 1.0 + x
+        if not (0.0 <= lo <= hi and math.isfinite(hi)):
+            raise ValueError(f"ColorJitter: {name} needs 0 <= lo <= hi, got ({lo}, {hi})")
+        return lo, hi
+
+    def sample(self, n_tiles: int, key) -> np.ndarray:
+        """-> float32 [n_tiles,4] rows of (fb, fc, fs, order), factors rounded to float32 here (the kernel and Pillow take them as they are)."""
+        n = int(n_tiles)
+        rng = np.random.default_rng(tuple(int(k) for k in key) + (1,))
+        u = [rng.random(n) for _ in range(3)]                                     # brightness, contrast, saturation
+        order = rng.integers(6, size=n)
+        u_gray, u_p = rng.random(n), rng.random(n)
+        out = np.empty((n, 4), dtype=np.float32)
+        for k, (lo, hi) in enumerate((self.brightness, self.contrast, self.saturation)):
+            out[:, k] = np.minimum(lo + u[k] * (hi - lo), hi).astype(np.float32)
+        out[u_gray < self.gray, 2] = 0.0
+        out[:, 3] = order
+        out[~(u_p < self.p)] = 1.0                                                 # the identity row (the order of three unit factors is immaterial)
+        return out
+
+
 class TrainAugment:
     """Deterministic host-side sampler of train-time crops, flips and mosaics, plus the box transform; the pixels are produced on the device by
     `DevicePrefetcher(..., augment=TrainAugment(size))` (or `DeviceImageProcessor.tiles`).
@@ -281,9 +379,13 @@ class TrainAugment:
     Targets: `sample` takes the sources' COCO `xywh` PIXEL boxes and returns, per output image, NORMALISED `xyxy` float32 boxes in [0, 1] and their labels
     (`transform_boxes`) -- the form `coco_to_model_input` returns, so the caller SKIPS that function for augmented batches.  `PackedTargets` needs at least one
     box per image: an output image left without one is redrawn up to `max_tries` times, then falls back to its whole, unflipped source at g = 1 with every box
-    kept; `fallbacks` counts those."""
+    kept; `fallbacks` counts those.
 
-    def __init__(self, size, *, mosaic=(1,), scale=(0.3, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, min_visibility=0.3, min_box=2.0, seed=0, rank=0, max_tries=10):
+    `color=ColorJitter(...)` adds per-tile brightness / contrast / saturation / grayscale on the resized cells: `sample_color(n_tiles, epoch, index)` draws the
+    tiles' (fb, fc, fs, order) rows from a stream of its own under the same key, so `sample` returns the same tiles, boxes and labels with colour on or off."""
+
+    def __init__(self, size, *, mosaic=(1,), scale=(0.3, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, min_visibility=0.3, min_box=2.0, seed=0, rank=0, max_tries=10,
+                 color=None):
         self.size = int(size)
         self.mosaic = tuple(int(g) for g in mosaic)
         if not self.mosaic or any(g < 1 or self.size % g for g in self.mosaic):
@@ -297,6 +399,15 @@ class TrainAugment:
         self.min_box = float(min_box)
         self.seed, self.rank, self.max_tries = int(seed), int(rank), int(max_tries)
         self.fallbacks = 0
+        if color is not None and not hasattr(color, "sample"):
+            raise TypeError("TrainAugment: color must be a ColorJitter (or None)")
+        self.color = color
+
+    def sample_color(self, n_tiles, epoch, index):
+        """The colour rows of the `n_tiles` tiles `sample` returned for batch `index` of epoch `epoch` -> float32 [n_tiles,4], or None without `color`."""
+        if self.color is None:
+            return None
+        return check_color(self.color.sample(n_tiles, (self.seed, self.rank, int(epoch), int(index))), n_tiles)
 
     def _crops(self, rng, H, W):
         """One crop per entry of the float64 arrays H, W -> [n,4] (left, upper, right, lower)."""
@@ -466,7 +577,8 @@ class DevicePrefetcher:
     `augment=TrainAugment(size)` (train loops only; eval never augments) turns on random crops, flips and mosaics: the loader must then yield
     `(images, labels, boxes, *rest)` with uint8 HWC images, per-image label tensors and per-image COCO `xywh` PIXEL boxes.  The staging thread draws the
     batch's tiles (keyed by the augment's seed and rank, `set_epoch`'s epoch and the batch's index), builds their tap tables and descriptors, ships them in
-    the same slab as the pixels and runs `owl_preprocess_u8_tiles` on the copy stream; it hands over `(pixel_values, labels, boxes, *rest)` with the boxes
+    the same slab as the pixels and runs `owl_preprocess_u8_tiles` on the copy stream (with `TrainAugment(..., color=ColorJitter(...))` the tiles' colour
+    rows ride in that slab too and the launch is `owl_preprocess_u8_tiles_color`; boxes and labels are the same either way); it hands over `(pixel_values, labels, boxes, *rest)` with the boxes
     already NORMALISED `xyxy` (skip `coco_to_model_input` for such batches).  `target_transform` then sees the augmented targets.  `threaded=True` pulls from the loader, stages and
     enqueues from a background thread (`depth` batches ahead); `threaded=False` does the same work inside `__next__`, one batch ahead.
     No CPU fallback: images are processed by libowlhip.so on the device or not at all."""
@@ -604,13 +716,14 @@ class DevicePrefetcher:
                 dev = self._h2d(list(items) + tensors)
                 img = self._images_on_device(kind, dev[:len(items)])
             else:
-                desc, arena, tmp_bytes, max_rows = plan
+                desc, arena, tmp_bytes, max_rows, color = plan
                 n = len(items)
-                extra = [torch.from_numpy(arena), torch.from_numpy(desc)]
+                extra = [torch.from_numpy(arena), torch.from_numpy(desc)] + ([torch.from_numpy(color)] if color is not None else [])
+                k = len(items) + len(tensors)                                      # arena, descriptors [, colour rows] ride behind the pixels and targets
                 dev = self._h2d(list(items) + tensors + extra,
-                                patch=lambda out: resolve_tile_descs(desc, [t.data_ptr() for t in out[:n]], out[-2].data_ptr()))
-                img = self.processor.run_tiles(dev[-1], desc.shape[0], max_rows, tmp_bytes, n)
-                dev = dev[:-2]
+                                patch=lambda out: resolve_tile_descs(desc, [t.data_ptr() for t in out[:n]], out[k].data_ptr()))
+                img = self.processor.run_tiles(dev[k + 1], desc.shape[0], max_rows, tmp_bytes, n, color=dev[k + 2] if color is not None else None)
+                dev = dev[:k]
             if tensors:
                 seq = {r: type(rest[r]) for r, j in where if j is not None}       # lists / tuples of tensors keep their type
                 rest = [list(o) if r in seq else o for r, o in enumerate(rest)]
@@ -643,9 +756,10 @@ class DevicePrefetcher:
         boxes = [np.asarray(torch.as_tensor(b), dtype=np.float64).reshape(-1, 4) for b in rest[1]]
         shapes = [(int(t.shape[0]), int(t.shape[1])) for t in items]
         tiles, ob, ol = self.augment.sample(shapes, boxes, labels, self._epoch, self._index)
+        color = self.augment.sample_color(len(tiles), self._epoch, self._index) if getattr(self.augment, "color", None) is not None else None
         self._index += 1
         check_tile_cover(tiles, len(items), self.size, shapes)
-        plan = build_tile_tables(shapes, tiles)
+        plan = build_tile_tables(shapes, tiles) + (color,)
         return items, ([torch.from_numpy(l) for l in ol], [torch.from_numpy(b) for b in ob]) + tuple(rest[2:]), plan
 
     # -- hand-over (the caller's thread and stream) ------------------------------------------------------------------------------------------------
