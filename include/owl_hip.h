@@ -170,6 +170,8 @@ int owl_push_pull_loss_bwd(void* stream, const float* g4, const int64_t* target_
  * offset boxes + class * (max + 1) then one class-agnostic NMS (_batched_nms_coordinate_trick), 2 / 3 torchvision's own choice for a
  * GPU / CPU tensor (coordinate trick up to 20 000 / 4 000 coordinates past the threshold).  They differ only where the f32 rounding of
  * the shifted coordinates moves an IoU across the threshold.
+ * The selection follows torch.max: a row with a NaN in any column is dropped, -0.0 == +0.0 (score ties: lower patch index first), and
+ * out_scores holds the winning column's own bits.
  * boxes [B,P,4] f32 xyxy, sims [B,P,C] f32 -> out_boxes [B,max_out,4], out_scores [B,max_out], out_classes [B,max_out] i64,
  * out_patch [B,max_out] i64 (source patch index), out_count [B] i32; entries beyond the count are left untouched.
  * workspace: device scratch of owl_postprocess_workspace() bytes (16-byte aligned); `bytes` is a HOST pointer.     */

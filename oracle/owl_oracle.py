@@ -306,8 +306,13 @@ def adamw_step(p, g, m, v, step, lr=3e-6, wd=0.1, b1=0.9, b2=0.999, eps=1e-8):
 # (IoU = inter / (area_a + area_b - inter), plain f32, intersection sides clamped at 0); result ordered by descending
 # score.  Ties in score: lower patch index first (what a stable sort gives).
 # PARITY NOTE: the max/threshold/index/shape part is pinned by running the reference's PostProcess (fixture F6, once per
-# route); the NMS inside those runs is this same restatement injected as the torchvision stub => "parity unpinned" for
-# torchvision's kernels themselves.
+# route) and, for NaN rows, signed zeros and score ties, against torch.max / a stable torch.sort themselves
+# (tests/test_postprocess_reference.py).  The NMS inside the F6 runs is this same restatement injected as the torchvision
+# stub.  What pins it independently is tests/postprocess_reference.py: a float64 greedy NMS with a derived per-pair f32
+# margin -- on an input where every same-group pair is decided by that margin, ANY correct f32 evaluation of the formula
+# (torchvision's CPU and GPU kernels included, in any operation order) returns the float64 list, and this restatement is
+# asserted equal to it on every such case.  "Parity unpinned" now means only the UNDECIDED pairs (an IoU within f32
+# round-off of the threshold, e.g. F6's last case): there the operation order decides, and only torchvision could settle it.
 # ---------------------------------------------------------------------------------------------------------------------
 def _nms_plain(boxes: np.ndarray, scores: np.ndarray, group, iou_threshold: float) -> np.ndarray:
     """Greedy NMS in f32 like torchvision's kernels; `group` (int array or None): only boxes of the same group suppress
@@ -372,8 +377,8 @@ def post_process(pred_boxes, pred_sims, confidence_threshold=0.75, iou_threshold
     already score-descending this is a prefix."""
     b = np.asarray(pred_boxes, np.float32)
     s = np.asarray(pred_sims, np.float32)
-    scores = s.max(axis=1)
-    classes = s.argmax(axis=1)                  # first maximal class, like torch.max on CPU
+    classes = s.argmax(axis=1)                  # first maximal class, like torch.max on CPU (a NaN row: its first NaN)
+    scores = s[np.arange(s.shape[0]), classes]  # that column's own bits, as torch.max returns them: [-0.0, +0.0] -> -0.0 (np.max may answer either zero)
     sel = np.nonzero(scores > np.float32(confidence_threshold))[0]
     keep = batched_nms(b[sel], scores[sel], classes[sel], iou_threshold, route)
     idx = sel[keep]

@@ -4,6 +4,8 @@
 //
 //   per image:  score_p = max_c sims[p][c], class_p = first arg-max        (ref models.py:132-134)
 //               keep p with score_p > confidence_threshold                 (ref models.py:136-139)
+//               -- torch.max's rules: a NaN in any column makes score_p NaN (the row is dropped); -0.0 == +0.0, in the arg-max
+//                  and in the order below (ties: lower patch index first); the emitted score is the winning column's own bits
 //               class-aware NMS, result ordered by descending score        (ref models.py:141-144)
 //               -- torchvision.ops.batched_nms has TWO routes (torchvision/ops/boxes.py) and both are here, selected per call by `route`:
 //                  0 per class on the raw coordinates (_batched_nms_vanilla); 1 coordinate offset: boxes + class * (max coordinate + 1) in
@@ -47,11 +49,14 @@ __global__ __launch_bounds__(1024) void pp_sort_kernel(const float* __restrict__
             const float* r = sims + ((int64_t)b * P + p) * C;
             float best = r[0];
             int arg = 0;
+            bool nan = best != best;                 // torch.max: a NaN in ANY column makes the row's maximum NaN, and NaN > conf drops the row
             for (int c = 1; c < C; c++) {
                 const float v = r[c];
+                nan |= v != v;
                 if (v > best) { best = v; arg = c; }
             }
-            if (best > conf) key = ((u64)(~orderable(best)) << 32) | ((u64)(unsigned)p << 16) | (u64)(unsigned)arg;
+            // -0.0 == +0.0 in the order (patch index breaks the tie, as a stable sort of the scores does): both zeros take +0.0's key
+            if (!nan && best > conf) key = ((u64)(~orderable(best == 0.f ? 0.f : best)) << 32) | ((u64)(unsigned)p << 16) | (u64)(unsigned)arg;
         }
         keys[p] = key;
     }
@@ -78,7 +83,7 @@ __global__ __launch_bounds__(1024) void pp_sort_kernel(const float* __restrict__
         const float4 bx = ((const float4*)boxes)[(int64_t)b * P + idx];
         ((float4*)s_box)[o] = bx;
         lmax = max(max(lmax, orderable(bx.x)), max(max(orderable(bx.y), orderable(bx.z)), orderable(bx.w)));
-        s_score[o] = unorderable(~(unsigned)(key >> 32));
+        s_score[o] = sims[((int64_t)b * P + idx) * C + cls];        // the input's own bits (the key holds one zero for both)
         s_cls[o] = cls;
         s_idx[o] = idx;
         if (p + 1 == P || keys[p + 1] == ~0ull) n_valid[b] = p + 1;
