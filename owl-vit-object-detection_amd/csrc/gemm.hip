@@ -539,7 +539,8 @@ OWL_API int owl_patch_embed_bf16(void* stream, const void* image_bf16, const voi
                                     float* x_out, void* scratch, int64_t B, int64_t S, int64_t ps, int64_t D, int64_t Tp, int tile) {
     OWL_CHECK_ARG(image_bf16 && w_pe && pos && x_out, "owl_patch_embed_bf16: null pointer");
     // (even patch sizes only: a 16-byte LDS-DMA piece starts at byte 2 * (row * S + px * ps + kx), which is 4-byte aligned -- what global_load_lds_dwordx4
-    //  needs -- only when ps, hence S, is even; tested: 14, 16, 24, 32)
+    //  needs -- only when ps, hence S, is even; tested: every even size 8 .. 64 on each kernel, bit for bit on integer data, with NaN patches, at an
+    //  8-byte-aligned image base and with byte offsets above 2^31 -- tests/test_embed_reference_gpu.py, profiles/embed_reference.md)
     OWL_CHECK_ARG(S % ps == 0 && ps >= 8 && ps <= 64 && ps % 2 == 0, "owl_patch_embed_bf16: image side must be a multiple of the patch size, patch size even and 8 <= patch size <= 64");
     const int64_t G = S / ps, P = G * G;
     int64_t psp = 8; while (psp < ps) psp *= 2;

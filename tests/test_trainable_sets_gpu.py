@@ -238,9 +238,10 @@ def test_embed_bwd_and_patch_weight_gradient_alone(B, grid, p, D):
     Tp = (T + 7) // 8 * 8
     g = torch.Generator().manual_seed(11)
     dx = torch.randn(B, Tp, D, generator=g)
-    dx[:, T:] = 1e6 * (1 + torch.rand(B, Tp - T, D, generator=g))        # pad rows hold LARGE values: they must not leak into any sum
+    dx[:, T:] = float("nan")                                             # pad rows hold NaN: they must not leak into any sum or row
     img = torch.randn(B, 3, S, S, generator=g).to(torch.bfloat16)
-    dE = torch.zeros(ops.pad_rows(B * P), D, dtype=torch.bfloat16, device=DEV)
+    dE_all = torch.full((ops.pad_rows(B * P) + 8, D), 0x4B5A, dtype=torch.int16, device=DEV).view(torch.bfloat16)      # 8 sentinel rows behind the buffer
+    dE = dE_all[:ops.pad_rows(B * P)]
     patches = torch.zeros(ops.pad_rows(B * P), (K + 7) // 8 * 8, dtype=torch.bfloat16, device=DEV)
     ops.im2row_bf16(img.to(DEV), patches, B, S, p)
     x64 = dx.double()
@@ -269,6 +270,7 @@ def test_embed_bwd_and_patch_weight_gradient_alone(B, grid, p, D):
         assert bool(((dcls.cpu().double() - (ref_pos[0] + s_cls.double())).abs() <= tol_c).all())
         # the packed bf16 rows: RNE of the patch rows, nothing else
         assert torch.equal(dE[:B * P].cpu(), ref_dE) and not bool(dE[B * P:].any())
+        assert bool((dE_all[ops.pad_rows(B * P):].view(torch.int16) == 0x4B5A).all())
         # weight gradient: bf16 operands (products exact in f32), f32 accumulation over B P terms in an order the test does not assume, plus the slab
         # reduction's adds (at most 256 splits) and the add into the value already there: |err| <= gamma2(B P + 257 [+ 1]) (sum |dE| |patches| + |seed|)
         # (tests/gemm_reference.py, any-order form)
@@ -278,6 +280,32 @@ def test_embed_bwd_and_patch_weight_gradient_alone(B, grid, p, D):
         assert bool((err_w <= tol_w).all())
     # im2row in the parameter's (c, i, j) order
     assert torch.equal(patches[:B * P, :K].cpu(), ref_patches) and not bool(patches[:, K:].any())
+
+
+@pytest.mark.parametrize("B,T,D", [(1, 2, 8), (3, 257, 8)])      # the smallest problem (one thread); T D / 8 = 257 threads: the second workgroup owns one token
+def test_embed_bwd_alone_at_the_edges_of_its_grid(B, T, D):
+    """owl_embed_bwd alone: dpos / dcls against float64 with the B-term bound of the test above, dE the RNE of the patch rows; pad rows T .. Tp of dx are
+    NaN, dE and dpos carry sentinel rows behind them."""
+    P, Tp = T - 1, (T + 7) // 8 * 8
+    g = torch.Generator().manual_seed(13 + T)
+    dx = torch.randn(B, Tp, D, generator=g)
+    dx[:, T:] = float("nan")
+    s_pos, s_cls = torch.randn(T, D, generator=g), torch.randn(D, generator=g)
+    dpos = torch.full((T + 2, D), 12345.678, device=DEV); dpos[:T] = s_pos.to(DEV)
+    dcls = torch.full((2, D), 12345.678, device=DEV); dcls[0] = s_cls.to(DEV)
+    dE = torch.full((B * P + 8, D), 0x4B5A, dtype=torch.int16, device=DEV).view(torch.bfloat16)
+    dx_dev = dx.to(DEV)
+    ops.embed_bwd(dx_dev, dpos, dcls, dE, B, T, Tp, D)
+    torch.cuda.synchronize()
+    x64 = dx.double()
+    ref = x64[:, :T].sum(0) + s_pos.double()
+    tol = B * 2.0 ** -24 * (x64[:, :T].abs().sum(0) + s_pos.double().abs())
+    assert bool(((dpos[:T].cpu().double() - ref).abs() <= tol).all())
+    ref_c = x64[:, 0].sum(0) + s_cls.double()
+    assert bool(((dcls[0].cpu().double() - ref_c).abs() <= B * 2.0 ** -24 * (x64[:, 0].abs().sum(0) + s_cls.double().abs())).all())
+    assert torch.equal(dE[:B * P].cpu(), dx[:, 1:T].reshape(B * P, D).to(torch.bfloat16))
+    assert bool((dE[B * P:].view(torch.int16) == 0x4B5A).all()) and bool((dpos[T:] == 12345.678).all()) and bool((dcls[1] == 12345.678).all())
+    assert torch.equal(dx_dev[:, :T].cpu(), dx[:, :T]) and bool(torch.isnan(dx_dev[:, T:]).all())
 
 
 # ---- 8. determinism ---------------------------------------------------------------------------------------------------------------------------
