@@ -178,6 +178,21 @@ int owl_push_pull_loss_bwd(void* stream, const float* g4, const int64_t* target_
 int owl_postprocess_workspace(int64_t B, int64_t P, int64_t* bytes);
 int owl_postprocess(void* stream, const float* boxes, const float* sims, void* workspace, int64_t ws_bytes, float* out_boxes, float* out_scores, int64_t* out_classes, int64_t* out_patch, int* out_count, int64_t B, int64_t P, int64_t C, int64_t max_out, float conf_thr, float iou_thr, int route);
 
+/* ---- sliced inference, the merge (csrc/slice_merge.hip): the candidates owl_postprocess left on T slices become one detection list per source image.
+ * boxes [T,K,4] f32, scores [T,K] f32, classes [T,K] i64, counts [T] i32 are owl_postprocess' outputs on the slices (slots past a slice's count are never
+ * read); xform [T,4] f32 rows (sx, ox, sy, oy) map a slice's box into its source image: x = ox + bx * sx, y = oy + by * sy (an f32 multiply, then an f32 add;
+ * no clipping); slice_offsets [G+1] i32 is a CSR over the G source images (device arrays, both).  Candidate c = local_slice * K + rank of a source image is
+ * live iff rank < counts[slice] and its score is not NaN; order: score descending, then c ascending, -0.0 == +0.0; out_scores keeps the input's bits.
+ * Greedy suppression of the lower-ranked candidate where the classes are equal (class_aware 1; any pair with 0) and ovr > thr; metric 0: ovr = inter /
+ * (ai + aj - inter), owl_postprocess' per-class route operation for operation; metric 1: ovr = inter / min(ai, aj) (intersection over the smaller area:
+ * a box cut by a slice border against the whole box from the neighbouring slice).  0 / 0 is NaN and suppresses nothing.  At most max_out per source image.
+ * Nmax >= K times the largest slice count of a group, <= 8192.  -> out_boxes [G,max_out,4] (full-image coordinates), out_scores [G,max_out], out_classes
+ * [G,max_out] i64, out_src [G,max_out] i64 (= c: c / K is the slice within the group, c % K the rank in it), out_count [G] i32; entries beyond the count
+ * are left untouched.  Three launches, no host sync.  workspace: owl_slice_merge_workspace() bytes of device scratch (16-byte aligned); `bytes` is a HOST
+ * pointer.  boxes, xform and out_boxes are 16-byte aligned.  Additive: the ABI version is unchanged.                                                       */
+int owl_slice_merge_workspace(int64_t G, int64_t Nmax, int64_t* bytes);
+int owl_slice_merge(void* stream, const float* boxes, const float* scores, const int64_t* classes, const int* counts, const float* xform, const int* slice_offsets, void* workspace, int64_t ws_bytes, float* out_boxes, float* out_scores, int64_t* out_classes, int64_t* out_src, int* out_count, int64_t T, int64_t K, int64_t G, int64_t Nmax, int64_t max_out, float thr, int metric, int class_aware);
+
 /* ---- COCO bbox mAP of the eval loop, on device (ref main.py:31,120-128,144-147; src/train_util.py:37-64 -> torchmetrics
  * MeanAveragePrecision(iou_type="bbox", class_metrics=True) -> the pycocotools COCOeval protocol evaluateImg / accumulate).  ABI 7.
  * The protocol's constants come from the caller as device arrays and are never re-derived in device code: iou_thr f64 [10] (linspace(0.5, 0.95, 10)),

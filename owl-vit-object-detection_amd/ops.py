@@ -416,6 +416,42 @@ def postprocess(boxes, sims, max_out, conf_thr, iou_thr, route="torchvision_gpu"
     return out_boxes, out_classes, out_scores, out_patch, counts
 
 
+_sm_ws = {}
+
+MERGE_METRICS = {"iou": 0, "ios": 1}
+SLICE_MERGE_MAX = 8192     # candidates per source image: the ceiling of the merge's LDS sort and of its scan's 128 mask words
+
+
+def slice_merge(boxes, scores, classes, counts, xform, slice_offsets, n_groups, n_max, max_out, thr, metric, class_aware):
+    """owl_slice_merge: boxes [T,K,4] f32, scores [T,K] f32, classes [T,K] i64, counts [T] i32 (= postprocess' outputs on T slices), xform [T,4] f32 rows
+    (sx, ox, sy, oy), slice_offsets [G+1] i32 (a CSR over the G source images), all on the device; n_max >= K * the largest slice count of a group;
+    metric 0 | "iou", 1 | "ios" -> (boxes [G,M,4] in full-image coordinates, classes [G,M] i64 (-1 pad), scores [G,M] (0 pad), src [G,M] i64 (-1 pad;
+    candidate index: src // K is the slice within its group, src % K the rank in it), counts [G] i32) with M = max_out."""
+    _chk(boxes, torch.float32, "boxes"); _chk(scores, torch.float32, "scores"); _chk(classes, torch.int64, "classes"); _chk(counts, torch.int32, "counts")
+    _chk(xform, torch.float32, "xform"); _chk(slice_offsets, torch.int32, "slice_offsets")
+    if boxes.dim() != 3 or boxes.shape[-1] != 4 or tuple(scores.shape) != tuple(boxes.shape[:2]) or tuple(classes.shape) != tuple(scores.shape):
+        raise ValueError(f"slice_merge: expected boxes [T,K,4], scores / classes [T,K], got {tuple(boxes.shape)} / {tuple(scores.shape)} / {tuple(classes.shape)}")
+    T, K = scores.shape
+    G, N, max_out = int(n_groups), int(n_max), int(max_out)
+    if tuple(counts.shape) != (T,) or tuple(xform.shape) != (T, 4) or tuple(slice_offsets.shape) != (G + 1,):
+        raise ValueError(f"slice_merge: expected counts [{T}], xform [{T},4], slice_offsets [{G + 1}], got {tuple(counts.shape)} / {tuple(xform.shape)} / {tuple(slice_offsets.shape)}")
+    dev = boxes.device
+    key = (G, N, dev)
+    if key not in _sm_ws:
+        nbytes = torch.zeros(1, dtype=torch.int64)
+        _lib.call("owl_slice_merge_workspace", G, N, nbytes)
+        _sm_ws[key] = torch.empty(int(nbytes.item()), dtype=torch.uint8, device=dev)
+    ws = _sm_ws[key]
+    out_boxes = torch.zeros(G, max_out, 4, dtype=torch.float32, device=dev)
+    out_scores = torch.zeros(G, max_out, dtype=torch.float32, device=dev)
+    out_classes = torch.full((G, max_out), -1, dtype=torch.int64, device=dev)
+    out_src = torch.full((G, max_out), -1, dtype=torch.int64, device=dev)
+    out_counts = torch.zeros(G, dtype=torch.int32, device=dev)
+    _lib.call("owl_slice_merge", stream(), boxes, scores, classes, counts, xform, slice_offsets, ws, ws.numel(), out_boxes, out_scores, out_classes,
+              out_src, out_counts, T, K, G, N, max_out, float(thr), int(MERGE_METRICS.get(metric, metric)), 1 if class_aware else 0)
+    return out_boxes, out_classes, out_scores, out_src, out_counts
+
+
 # ---- COCO bbox mAP of the eval loop (csrc/metrics.hip).  The protocol's constants are made ONCE on the host, exactly as pycocotools makes them,
 # and handed to the kernels as arrays: device code never re-derives a threshold.
 MAP_T, MAP_R, MAP_A, MAP_M = 10, 101, 4, 3

@@ -126,6 +126,15 @@ class DeviceImageProcessor:
         self._keep = (imgs, arena_d, desc_d, color_d)          # keep the sources and tables alive until the stream has consumed them
         return out
 
+    def slices(self, images, slice_size=None, overlap=0.2, full_image=True):
+        """Sliced inference's input: every window of `slice_plan` resampled to one size x size canvas -> (pixel_values [T,3,S,S], plan).  A slice is a tile
+        whose cell is the whole canvas, so this is `tiles()` unchanged and each canvas is Pillow's `resize((S, S), BICUBIC, box=window)` followed by the
+        table.  `slice_size=None`: windows of the processor's own size (one model pixel per source pixel)."""
+        imgs = [self._to_device(im) for im in (list(images) if isinstance(images, (list, tuple)) else [images])]
+        shapes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
+        plan = slice_plan(shapes, self.size if slice_size is None else slice_size, overlap, full_image, size=self.size)
+        return self.tiles(imgs, plan.tiles, len(plan.tiles)), plan
+
     def normalize_sized(self, src_u8: torch.Tensor, chw: bool) -> torch.Tensor:
         """Images that already have the model's size: u8 [B,S,S,3] (chw=False) or [B,3,S,S] (chw=True) ON THE DEVICE -> [B,3,S,S] self.dtype.  Pillow's resize to
         the size an image already has is a copy, so only the table step of the reference pipeline is left (owl_normalize_u8)."""
@@ -188,6 +197,56 @@ def check_tile_cover(tiles, n_out: int, size: int, shapes=None):
         if bad.any():
             t = tiles[int(np.flatnonzero(bad)[0])]
             raise ValueError(f"tiles: box {tuple(t.box)} is empty or outside its {shapes[t.src][1]} x {shapes[t.src][0]} source")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Sliced inference: the slice grid.  A large image is cut into overlapping windows, each window becomes one full-resolution model input (a tile whose
+# cell is the whole canvas), and the per-slice detections are mapped back with `xform` and merged on the device (csrc/slice_merge.hip,
+# postprocess.SlicedPostProcess).  Pure numpy: nothing here needs a GPU.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+SlicePlan = namedtuple("SlicePlan", "tiles slice_offsets xform shapes")
+
+
+def slice_starts(n: int, s: int, overlap: float):
+    """The (lo, hi) windows of one axis of length n: the single window (0, n) if n <= s; else windows of length s every s - int(s * overlap), the first one
+    that would pass n replaced by (n - s, n), which ends the list (so the last window is flush with the axis and overlaps its neighbour at least as much).
+    A window that ends exactly at n ends the list too: no window is cut twice."""
+    n, s = int(n), int(s)
+    if n <= 0 or s <= 0:
+        raise ValueError(f"slice_starts: need n > 0 and s > 0 (n={n} s={s})")
+    if n <= s:
+        return [(0, n)]
+    step = s - int(s * overlap)
+    if not 1 <= step <= s:
+        raise ValueError(f"slice_starts: overlap {overlap} of a window of {s} leaves a step of {step}; need 1 <= step <= {s}")
+    out, p = [], 0
+    while p + s <= n:
+        out.append((p, p + s))
+        if p + s == n:
+            return out
+        p += step
+    out.append((n - s, n))
+    return out
+
+
+def slice_plan(shapes, slice_size, overlap=0.2, full_image=True, size=None):
+    """shapes: the sources' (H, W).  Per source the row-major product of its two axes' `slice_starts` windows as boxes (left, upper, right, lower), plus --
+    with `full_image` and more than one window -- the whole image as one more slice (what finds the objects larger than a window).  -> SlicePlan(
+    tiles: one Tile(src, box, False, t, 0, 0, S, S) per slice (S = `size`, default slice_size); slice_offsets int32 [G + 1], a CSR over the sources;
+    xform float32 [T, 4] rows (sx, ox, sy, oy) = ((right - left) / W, left / W, (lower - upper) / H, upper / H), each quotient formed in float64 and rounded
+    once: a slice's normalised box maps into its source as x = ox + bx * sx, y = oy + by * sy; shapes)."""
+    S = int(slice_size if size is None else size)
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    tiles, offs, xf = [], [0], []
+    for g, (H, W) in enumerate(shapes):
+        boxes = [(l, u, r, lo) for (u, lo) in slice_starts(H, slice_size, overlap) for (l, r) in slice_starts(W, slice_size, overlap)]
+        if full_image and len(boxes) > 1:
+            boxes.append((0, 0, W, H))
+        for (l, u, r, lo) in boxes:
+            tiles.append(Tile(g, (l, u, r, lo), False, len(tiles), 0, 0, S, S))
+            xf.append(((r - l) / W, l / W, (lo - u) / H, u / H))
+        offs.append(len(tiles))
+    return SlicePlan(tiles, np.asarray(offs, dtype=np.int32), np.asarray(xf, dtype=np.float64).reshape(-1, 4).astype(np.float32), shapes)
 
 
 def _ksize(extent: float, out: int) -> int:
