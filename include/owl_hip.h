@@ -389,9 +389,9 @@ int owl_image_query_workspace_bytes(int64_t N, int64_t P, int64_t Dt, int64_t* n
 int owl_image_query_select(void* stream, const float* e, const float* boxes, const float* qbox, int64_t N, int64_t P, int64_t Dt, void* workspace, int64_t workspace_bytes, int* best, float* query, int* info, float* v_out, double* mean_out, double* sim_out);
 int owl_query_bank_fill(void* stream, const float* query, const int* row_ptr, const int* members, float* bank, int64_t N, int64_t nq, int64_t Dt);
 
-/* ---- open-vocabulary class head, forward only (still ABI 8: additive; csrc/open_vocab.hip, models.OwlViT.detect / detect_text) ----------------------
- * HF's OwlViTClassPredictionHead over query banks that differ per image (text prompts, or an image exemplar's embedding).  Inference only: there is
- * no backward, nothing is trained through it, and the fine-tuning head's kernels are untouched.  For image b, patch p, query q:
+/* ---- open-vocabulary class head, forward (still ABI 8: additive; csrc/open_vocab.hip, models.OwlViT.detect / detect_text / forward_queries) ----------
+ * HF's OwlViTClassPredictionHead over query banks that differ per image (text prompts, or an image exemplar's embedding).  Its adjoint is
+ * owl_class_logits_bwd below (fine-tuning through this head: models.OwlViT.forward_queries); the bank head's kernels are untouched.  For image b, patch p, query q:
  *     e^_p     = e_p / (|e_p| + 1e-6)              e  f32 [B P, Dt]: the class head's dense0 output
  *     q^_{b,q} = Q_{b,q} / (|Q_{b,q}| + 1e-6)      queries f32 [nbanks, Q, Dt], nbanks = B (a bank per image) or 1 (one bank for the batch).  HF's epsilon
  *                                                  placement, not owl_query_normalize's; an all-zero row (HF's padded query) stays all-zero, never NaN
@@ -407,6 +407,24 @@ int owl_query_bank_fill(void* stream, const float* query, const int* row_ptr, co
  *   16-byte aligned.  Two launches, no atomics, nothing allocated, no host sync; two runs give equal bits, and an image's block or a query's column
  *   carries the same bits wherever it stands in the batch or the bank.                                                                               */
 int owl_class_logits_fwd(void* stream, const float* e, const float* queries, const void* feats_bf16, const float* w_shift, const float* b_shift, const float* w_scale, const float* b_scale, const unsigned char* mask, float* rowstats, float* logits, float* scores, int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t nmasks, int64_t Dt, int64_t D);
+
+/* ---- open-vocabulary class head, backward (still ABI 8: additive; csrc/open_vocab_bwd.hip, models.OwlViT.forward_queries) ----------------------------
+ * The adjoint of owl_class_logits_fwd on the forward's operands: e, queries, mask as there, rowstats f32 [B P, 2] = the (shift, scale) the forward left.
+ * With g = dlogits f32 [B, P, Q] SELECTED to 0 where mask[b, q] == 0 (Inf / NaN there changes nothing), for row r of image b:
+ *     T_r = sum_q g[r, q] q^_{b,q}     gs_r = sum_q g[r, q]     c_r = e^_r . T_r     (= sum_q g cos; the cosine term is never recovered as logit / scale)
+ *     dshift = scale gs    dscale = c + shift gs    ds = dscale (scale > 1 ? 1 : scale)          ELU' read from the saved scale
+ *     dfeats f32 [B P, D]  = dshift w_shift + ds w_scale: a plain store of the shift / scale term (may be NULL: not formed)
+ *     de bf16 [B P, Dt]    = inv scale (T - e c / |e|), inv = 1 / (|e| + 1e-6); an all-zero row of e gives d(e^) / 1e-6, never NaN; finite where scale = 0
+ *     dqueries f32 [nbanks, Q, Dt] = (dq^ - u (q^ . dq^)) / (|Q| + 1e-6), dq^_{b,q} = sum over image b's rows (a shared bank: every image's) of
+ *                            g[r, q] inv_r scale_r e_r, u = Q / |Q| (0 for an all-zero row).  Plain store; a masked query's row is exactly 0.  May be NULL: the
+ *                            work is skipped and de / dfeats keep their bits.
+ *   T and dq^ run on v_mfma_f32_32x32x2f32 (f32 operands throughout); dq^ is summed per chunk of an image's rows into slabs of the workspace, which are
+ *   added in index order.  32-row tiles never straddle two images; rows >= B P of every output are not written.  Four launches (two without dqueries), no
+ *   atomics, nothing allocated, no host sync; every summation order is a function of (P, Q, Dt) alone: two runs give equal bits and an image's blocks are
+ *   the same alone or anywhere in the batch.  workspace: owl_class_logits_bwd_workspace_bytes(..., want_dq = dqueries != NULL), 16-byte aligned, contents
+ *   irrelevant.  Limits: the forward's (1 <= Q <= 4096, Dt % 64 == 0, Dt <= 1024, D % 8 == 0, 1 <= P <= 8192); w_shift, w_scale, dfeats 16-byte aligned. */
+int owl_class_logits_bwd_workspace_bytes(int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t Dt, int want_dq, int64_t* bytes);
+int owl_class_logits_bwd(void* stream, const float* dlogits, const float* e, const float* queries, const float* w_shift, const float* w_scale, const float* rowstats, const unsigned char* mask, void* workspace, int64_t workspace_bytes, void* de_bf16, float* dfeats, float* dqueries, int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t nmasks, int64_t Dt, int64_t D);
 
 /* ---- utilities ------------------------------------------------------------------------------------ */
 int owl_cast_f32_bf16(void* stream, const float* in, void* out, int64_t n);

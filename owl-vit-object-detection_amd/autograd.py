@@ -89,6 +89,51 @@ class OwlViTFunction(torch.autograd.Function):
         return (None, None, None) + (None,) * len(model.flat_offsets)
 
 
+class OwlViTQueryFunction(torch.autograd.Function):
+    """models.OwlViT.forward_queries with grad enabled: the same forward, HF's class head (ops.class_logits) over the caller's per-image queries on the
+    training workspace's e / feats, and backward_impl with the class-head adjoint switched to ops.class_logits_bwd.  The learnable bank takes no part;
+    `query_embeds` receives its gradient as an ordinary autograd gradient when it requires one."""
+
+    @staticmethod
+    def forward(ctx, model, image, query_embeds, query_mask, *params):
+        boxes, _ = model._forward_impl(image, save=True)
+        B = image.shape[0]
+        logits = model._class_logits_on(model._workspace(B), B, query_embeds, query_mask)
+        ctx.model, ctx.B = model, B
+        ctx.gen = model._workspace(B)["gen"]
+        ctx.qe, ctx.qm = query_embeds.detach(), query_mask
+        return boxes, logits
+
+    @staticmethod
+    def backward(ctx, d_boxes, d_logits):
+        model, B = ctx.model, ctx.B
+        if model._workspace(B)["gen"] != ctx.gen:
+            raise RuntimeError(
+                f"OwlViT backward: the activations of this forward (batch size {B}) were overwritten by a later gradient-recording "
+                "forward at the same batch size (or evicted: only the model's `max_cached_batch_sizes` most recent batch sizes keep their "
+                "workspaces); call backward() before the next training forward (no-grad / eval forwards are fine)")
+        dq = torch.empty_like(ctx.qe) if ctx.needs_input_grad[2] else None
+        head = dict(dlogits=d_logits, queries=ctx.qe, mask=ctx.qm, dq=dq, event=None)
+        if getattr(model, "overlap_tail", False) and d_boxes.is_cuda:
+            main, ts = torch.cuda.current_stream(), model._tail_stream
+            ts.wait_stream(main)
+            for t in (d_boxes, d_logits, ctx.qe, ctx.qm, dq):
+                if t is not None:
+                    t.record_stream(ts)           # (allocated on the compute stream, used on the tail stream)
+            with torch.cuda.stream(ts):
+                if dq is not None:
+                    head["event"] = torch.cuda.Event()          # recorded where the query gradient is complete, not at the tail's end
+                backward_impl(model, B, d_boxes, None, None, logit_head=head)
+                ev = torch.cuda.Event()
+                ev.record(ts)
+            model._param_event = ev
+            if dq is not None:
+                main.wait_event(head["event"])    # the query gradient goes back to the caller's stream: ordered here
+        else:
+            backward_impl(model, B, d_boxes, None, None, logit_head=head)
+        return (None, None, dq, None) + (None,) * len(model.flat_offsets)
+
+
 def _bws(model, B):
     key = ("bwd", B)
     if key in model._ws:
@@ -245,7 +290,11 @@ def patch_weight_grad(dE, patches, grad_w, D, K, rows, scratch=None, accumulate=
     weight_grad(dE, patches, grad_w, D, K, rows, scratch, accumulate=accumulate)
 
 
-def backward_impl(model, B, d_boxes, d_sims, sims):
+def backward_impl(model, B, d_boxes, d_sims, sims, logit_head=None):
+    """logit_head (None = the bank head's adjoint, today's launches): dict(dlogits [B, P, Q], queries, mask, dq, event) -- the class-head section is then
+    the adjoint of ops.class_logits (OwlViTQueryFunction): class_logits_bwd writes de and the shift / scale part of d(feats), dense0's dW runs as ever,
+    its dX GEMM ACCUMULATES into d(feats), then the box head's does: one fixed order of the three contributions.  `dq` (or None) receives the query
+    gradient and `event` (or None) is recorded on the calling stream once it is complete.  d_sims / sims are not read."""
     cfg = model.cfg
     D, I, H, Tp, T, P, Dt, C = cfg.hidden, cfg.mlp, cfg.heads, cfg.tokens_padded, cfg.tokens, cfg.patches, cfg.text_dim, cfg.n_classes
     M, Mh = B * Tp, B * P
@@ -262,7 +311,10 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
     below_enc = floor in ("pre_layernorm", "embeddings")
     LP = lambda i: f"backbone.encoder.layers.{i}."
     d_boxes = d_boxes.contiguous().float()
-    d_sims = d_sims.contiguous().float()
+    if logit_head is None:
+        d_sims = d_sims.contiguous().float()
+    else:
+        d_logits = logit_head["dlogits"].contiguous().float()
 
     # the forward launched the transposes on their own stream (models.OwlViT._pretranspose_weights): order this stream behind them once
     pre_wt = model._wt if (getattr(model, "pretranspose", False) and model._wt_event is not None) else None
@@ -298,7 +350,22 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
     cdw, cw = (bw["dw_class"], bw["wT2"]) if hs is not main0 else (bw["dw_main"], bw["wT"])
     # ---- class head ---------------------------------------------------------------------------------
     with torch.cuda.stream(hs):
-        if t_q or t_cls or below_heads:
+        if logit_head is not None:
+            # HF's class head over the caller's queries (csrc/open_vocab_bwd.hip); the learnable bank takes no part
+            dq = logit_head["dq"]
+            if t_cls or below_heads or dq is not None:
+                lh, qe, qm = model.logit_head, logit_head["queries"], logit_head["mask"]
+                nbanks = B if qe.dim() == 3 else 1
+                key, need = "ovb", ops.class_logits_bwd_workspace_bytes(B, P, qe.shape[-2], nbanks, Dt, dq is not None)
+                if key not in bw or bw[key].numel() < need:          # (one buffer per batch size, grown to the largest query count seen)
+                    bw[key] = torch.empty(need, dtype=torch.uint8, device=model.device_)
+                ops.class_logits_bwd(d_logits, ws["e"], qe, lh["logit_shift.weight"], lh["logit_scale.weight"], ws["logit_rowstats"], B, P, mask=qm,
+                                     de=bw["de"], dfeats=bw["dfeats"] if below_heads else False, dqueries=dq if dq is not None else False, workspace=bw[key])
+                if t_cls:
+                    weight_grad(bw["de"], ws["feats"], G("class_predictor.dense0.weight"), Dt, D, Mh, cdw, G("class_predictor.dense0.bias"))
+                if below_heads:
+                    ops.gemm(ops.EPI_ACC_F32, bw["de"], wT("class_predictor.dense0.weight", Dt, D, buf=cw), bw["dfeats"], M=Mh, N=D, K=Dt)
+        elif t_q or t_cls or below_heads:
             if model.wide_head:          # label sets beyond 10 classes: de as a dense f32-MFMA product, G [rows, Qp] in the wide query layout (csrc/class_head_wide.hip)
                 Qp = bw["g32"].shape[1]
                 ops.class_sims_wide_bwd(d_sims, sims, ws["argmax"], ws["inv_norm"], ws["e"], ws["qhat"], bw["de"], bw["g32"], bw["e_bf"], Mh, Dt, C)
@@ -335,6 +402,8 @@ def backward_impl(model, B, d_boxes, d_sims, sims):
             w0T = wT("box_head.dense0.weight", D, D)
     if hs is not main0:
         main0.wait_event(ev_h[1])                 # d(feats) of the class head is in place (and the side stream's scratch is free again)
+    if logit_head is not None and logit_head.get("event") is not None:
+        logit_head["event"].record(main0)         # the query gradient is complete on this stream from here on
     if not below_heads:
         return
     ops.gemm(ops.EPI_ACC_F32, bw["du0"], w0T, bw["dfeats"], M=Mh, N=D, K=D)

@@ -971,7 +971,7 @@ class OwlViT(nn.Module):
         `image_guided_detection` for one exemplar.  HF's post-processing is `PostProcess(confidence_threshold=t, iou_threshold=1.0)(pred_boxes, scores)`
         (the class is the arg-max query; an IoU threshold of 1 keeps everything, HF's `post_process_object_detection` has no NMS).
 
-        Needs `set_logit_head` (RuntimeError otherwise).  Inference only: nothing is trained through this head.  Runs the plain eval forward on the EVAL
+        Needs `set_logit_head` (RuntimeError otherwise).  Inference only; `forward_queries` is the gradient-recording form.  Runs the plain eval forward on the EVAL
         workspace behind a deferred optimizer tail (a pending training backward is not disturbed), in chunks of at most 32 images; the frozen-prefix
         cache is neither read nor written; `forward` and its outputs are untouched.  No host sync."""
         if self.logit_head is None:
@@ -1010,24 +1010,75 @@ class OwlViT(nn.Module):
         may differ per image, padded queries all-zero ids; or [Q, S] for one list shared by the batch.  A 2-D input whose row count is a multiple of B
         is read as [B Q, S] unless shared=True.  The embeddings are `text_tower.encode(ids)` (text.TextTower: the unit rows HF feeds its head), the
         mask is ids[..., 0] > 0 as in HF.  -> detect's result."""
-        B = int(pixel_values.shape[0])
-        ids = torch.as_tensor(np.asarray(input_ids) if not torch.is_tensor(input_ids) else input_ids)
-        if ids.dim() == 3:
-            if ids.shape[0] != B:
-                raise ValueError(f"detect_text: input_ids must be [{B}, Q, S], [{B} Q, S] or [Q, S], got {tuple(ids.shape)}")
-            shape = (B, int(ids.shape[1]))
-        elif ids.dim() == 2:
-            if shared is None:
-                shared = ids.shape[0] % B != 0
-            if not shared and ids.shape[0] % B:
-                raise ValueError(f"detect_text: input_ids [{ids.shape[0]}, S] is not [{B} Q, S] for a batch of {B} images")
-            shape = (int(ids.shape[0]),) if shared else (B, int(ids.shape[0]) // B)
-        else:
-            raise ValueError(f"detect_text: input_ids must be [{B}, Q, S], [{B} Q, S] or [Q, S], got {tuple(ids.shape)}")
-        flat = ids.reshape(-1, ids.shape[-1])
-        embeds = text_tower.encode(flat).reshape(*shape, -1)
-        mask = (flat[:, 0] > 0).reshape(*shape)
+        embeds, mask = text_queries("detect_text", int(pixel_values.shape[0]), input_ids, text_tower, shared)
         return self.detect(pixel_values, embeds, mask, return_scores=return_scores)
+
+    # -- open-vocabulary fine-tuning: the same head, gradient-recording ---------------------------------------------------------
+    def _class_logits_on(self, ws, B, qe, qm):
+        """HF's class head on a workspace's e / feats -> logits [B, P, Q]; (shift, scale) per row stay in ws["logit_rowstats"] for the adjoint."""
+        lh, P = self.logit_head, self.cfg.patches
+        if "logit_rowstats" not in ws:
+            ws["logit_rowstats"] = torch.zeros(B * P, 2, dtype=torch.float32, device=self.device_)
+        return ops.class_logits(ws["e"], qe, ws["feats"], lh["logit_shift.weight"], lh["logit_shift.bias"], lh["logit_scale.weight"], lh["logit_scale.bias"],
+                                B, P, mask=qm, rowstats=ws["logit_rowstats"])[0]
+
+    def forward_queries(self, pixel_values, query_embeds, query_mask=None):
+        """The gradient-recording form of `detect`: -> (pred_boxes [B, P, 4] corners, logits [B, P, Q]) of HF's class head over the caller's queries,
+        arguments as for `detect` (a bank per image [B, Q, Dt] or one shared [Q, Dt], an optional mask; masked logits are finfo(f32).min and pass no
+        gradient -- select them out of the loss).  Needs `set_logit_head` (RuntimeError otherwise).
+
+        With grad enabled the forward runs on the TRAINING workspace, pred_boxes carry the bits of `model(image)[0]`, and backward() accumulates into
+        the model's trainable set -- any set `trainable=` accepts -- exactly as the bank path does (flat_grad, FusedAdamW, the deferred tail), through
+        csrc/open_vocab_bwd.hip instead of the bank head's adjoint.  What is NOT trained: the learnable bank `queries` (it takes no part and gets no
+        gradient), the four logit-head tensors (frozen buffers; the gradient passes through them to the features) and any text tower.  If
+        `query_embeds.requires_grad` it receives its gradient as an ordinary autograd gradient (prompt tuning: the tensor is the caller's, stepped by
+        any torch optimizer; under the deferred tail the caller's stream is ordered behind it).  As with `forward`, call backward() before the next
+        recording forward at the same batch size (RuntimeError otherwise).  The loss over [B, P, Q] logits is the caller's torch code.
+
+        Under no_grad it is `detect`."""
+        if self.logit_head is None:
+            raise RuntimeError("forward_queries: no logit head -- call model.set_logit_head(weights.hf_logit_head(hf_state_dict)) or load_model(..., logit_head=)")
+        B, Q, shared = check_detect_args(self.cfg, pixel_values, query_embeds, query_mask)
+        qe = torch.as_tensor(query_embeds)
+        need_grad = torch.is_grad_enabled() and (qe.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if not need_grad:
+            return self.detect(pixel_values, qe.detach(), query_mask)
+        self._check_trainable_set()
+        qe = qe.to(self.device_).contiguous()          # (autograd-recorded: the gradient finds its way back to the caller's tensor)
+        qm = None
+        if query_mask is not None:
+            qm = (torch.as_tensor(query_mask).to(self.device_) != 0).to(torch.uint8).contiguous()
+        from .autograd import OwlViTQueryFunction
+        return OwlViTQueryFunction.apply(self, pixel_values, qe, qm, *[self._byname[n] for n in self.flat_offsets])
+
+    def forward_text(self, pixel_values, input_ids, text_tower, shared=None):
+        """`forward_queries` on tokenised prompts, input_ids laid out as for `detect_text`.  The text tower stays forward-only: its embeddings are
+        detached constants (nothing is trained in it)."""
+        with torch.no_grad():
+            embeds, mask = text_queries("forward_text", int(pixel_values.shape[0]), input_ids, text_tower, shared)
+        return self.forward_queries(pixel_values, embeds.detach(), mask)
+
+
+def text_queries(who, B, input_ids, text_tower, shared=None):
+    """The id layouts of detect_text / forward_text -> (embeds [B, Q, Dt] or [Q, Dt] = text_tower.encode(ids), mask = ids[..., 0] > 0 of the same
+    leading shape).  ValueError (prefixed `who`) names the layouts."""
+    ids = torch.as_tensor(np.asarray(input_ids) if not torch.is_tensor(input_ids) else input_ids)
+    if ids.dim() == 3:
+        if ids.shape[0] != B:
+            raise ValueError(f"{who}: input_ids must be [{B}, Q, S], [{B} Q, S] or [Q, S], got {tuple(ids.shape)}")
+        shape = (B, int(ids.shape[1]))
+    elif ids.dim() == 2:
+        if shared is None:
+            shared = ids.shape[0] % B != 0
+        if not shared and ids.shape[0] % B:
+            raise ValueError(f"{who}: input_ids [{ids.shape[0]}, S] is not [{B} Q, S] for a batch of {B} images")
+        shape = (int(ids.shape[0]),) if shared else (B, int(ids.shape[0]) // B)
+    else:
+        raise ValueError(f"{who}: input_ids must be [{B}, Q, S], [{B} Q, S] or [Q, S], got {tuple(ids.shape)}")
+    flat = ids.reshape(-1, ids.shape[-1])
+    embeds = text_tower.encode(flat).reshape(*shape, -1)
+    mask = (flat[:, 0] > 0).reshape(*shape)
+    return embeds, mask
 
 
 def check_detect_args(cfg, pixel_values, query_embeds, query_mask=None):

@@ -180,7 +180,7 @@ CLASS_LOGITS_MAX_QUERIES = 4096     # ceiling of class_logits (csrc/open_vocab.h
 
 
 def class_logits(e, queries, feats, w_shift, b_shift, w_scale, b_scale, B, P, mask=None, rowstats=None, logits=None, scores=False):
-    """HF's OwlViTClassPredictionHead over per-image query banks (include/owl_hip.h owl_class_logits_fwd; inference only, no backward):
+    """HF's OwlViTClassPredictionHead over per-image query banks (include/owl_hip.h owl_class_logits_fwd; its adjoint is class_logits_bwd):
     logits[b, p, q] = (e^_p . q^_{b,q} + shift_p) * scale_p with HF's q / (|q| + 1e-6), finfo(f32).min where mask == 0.
     e f32 [>= B P, Dt]; queries f32 [B, Q, Dt] or [Q, Dt] (one bank for the batch, read where it lies); feats bf16 [>= B P, D]; w_shift / w_scale f32 [D];
     b_shift / b_scale f32 device tensors of one element; mask uint8 [B, Q] or [Q] (nonzero = valid) or None.  rowstats (f32 [>= B P, 2] scratch: (shift,
@@ -222,6 +222,75 @@ def class_logits(e, queries, feats, w_shift, b_shift, w_scale, b_scale, B, P, ma
     _lib.call("owl_class_logits_fwd", stream(), e, queries, feats, w_shift, b_shift, w_scale, b_scale, mask, rowstats, logits, scores,
               B, P, Q, B if queries.dim() == 3 else 1, (B if mask.dim() == 2 else 1) if mask is not None else 1, Dt, D)
     return logits, scores, rowstats
+
+
+def class_logits_bwd_workspace_bytes(B, P, Q, nbanks, Dt, want_dq=True):
+    """Bytes of class_logits_bwd's workspace (include/owl_hip.h owl_class_logits_bwd_workspace_bytes): a host computation, no device is touched."""
+    nbytes = torch.zeros(1, dtype=torch.int64)
+    _lib.call("owl_class_logits_bwd_workspace_bytes", int(B), int(P), int(Q), int(nbanks), int(Dt), 1 if want_dq else 0, nbytes)
+    return int(nbytes.item())
+
+
+def class_logits_bwd(dlogits, e, queries, w_shift, w_scale, rowstats, B, P, mask=None, de=None, dfeats=True, dqueries=True, workspace=None):
+    """The adjoint of class_logits (include/owl_hip.h owl_class_logits_bwd) on the forward's operands; rowstats is what that forward left.
+    dlogits f32 [B, P, Q] (masked entries are selected to 0: anything may stand there); e f32 [>= B P, Dt]; queries f32 [B, Q, Dt] or [Q, Dt];
+    w_shift / w_scale f32 [D]; rowstats f32 [>= B P, 2]; mask uint8 [B, Q] or [Q] or None.
+    de: bf16 [>= B P, Dt], allocated when None.  dfeats / dqueries: True (allocate: f32 [B P, D] / f32 of queries' shape), False (not formed: the work
+    is skipped) or the tensor to store into (dfeats f32 [>= B P, D]).  workspace: a uint8 device tensor of at least
+    class_logits_bwd_workspace_bytes(...) bytes, allocated when None.  -> (de, dfeats or None, dqueries or None).  No host sync."""
+    _chk(dlogits, torch.float32, "dlogits"); _chk(e, torch.float32, "e"); _chk(queries, torch.float32, "queries")
+    _chk(w_shift, torch.float32, "w_shift"); _chk(w_scale, torch.float32, "w_scale"); _chk(rowstats, torch.float32, "rowstats"); _chk(mask, torch.uint8, "mask")
+    B, P = int(B), int(P)
+    if queries.dim() not in (2, 3) or (queries.dim() == 3 and queries.shape[0] != B):
+        raise ValueError(f"class_logits_bwd: queries must be [{B}, Q, Dt] or [Q, Dt], got {tuple(queries.shape)}")
+    Q, Dt = int(queries.shape[-2]), int(queries.shape[-1])
+    D = int(w_shift.numel())
+    if tuple(dlogits.shape) != (B, P, Q):
+        raise ValueError(f"class_logits_bwd: dlogits must be [{B}, {P}, {Q}], got {tuple(dlogits.shape)}")
+    if e.dim() != 2 or e.shape[1] != Dt or e.shape[0] < B * P:
+        raise ValueError(f"class_logits_bwd: e must be [>= {B * P}, {Dt}], got {tuple(e.shape)}")
+    if w_scale.numel() != D:
+        raise ValueError(f"class_logits_bwd: w_shift / w_scale must be [D] alike, got {w_shift.numel()} and {w_scale.numel()} elements")
+    if not 1 <= Q <= CLASS_LOGITS_MAX_QUERIES:
+        raise ValueError(f"class_logits_bwd: 1 <= Q <= {CLASS_LOGITS_MAX_QUERIES} queries per image, got {Q}")
+    if rowstats.numel() < 2 * B * P:
+        raise ValueError(f"class_logits_bwd: rowstats must hold [{B * P}, 2] floats")
+    if mask is not None and tuple(mask.shape) not in ((B, Q), (Q,)):
+        raise ValueError(f"class_logits_bwd: mask must be [{B}, {Q}] or [{Q}], got {tuple(mask.shape)}")
+    dev = e.device
+    if de is None:
+        de = torch.empty(B * P, Dt, dtype=torch.bfloat16, device=dev)
+    else:
+        _chk(de, torch.bfloat16, "de")
+        if de.dim() != 2 or de.shape[1] != Dt or de.shape[0] < B * P:
+            raise ValueError(f"class_logits_bwd: de must be bf16 [>= {B * P}, {Dt}], got {tuple(de.shape)}")
+    if dfeats is True:
+        dfeats = torch.empty(B * P, D, dtype=torch.float32, device=dev)
+    elif dfeats is False:
+        dfeats = None
+    else:
+        _chk(dfeats, torch.float32, "dfeats")
+        if dfeats.dim() != 2 or dfeats.shape[1] != D or dfeats.shape[0] < B * P:
+            raise ValueError(f"class_logits_bwd: dfeats must be f32 [>= {B * P}, {D}], got {tuple(dfeats.shape)}")
+    if dqueries is True:
+        dqueries = torch.empty_like(queries)
+    elif dqueries is False:
+        dqueries = None
+    else:
+        _chk(dqueries, torch.float32, "dqueries")
+        if tuple(dqueries.shape) != tuple(queries.shape):
+            raise ValueError(f"class_logits_bwd: dqueries must be f32 {tuple(queries.shape)}, got {tuple(dqueries.shape)}")
+    nbanks = B if queries.dim() == 3 else 1
+    need = class_logits_bwd_workspace_bytes(B, P, Q, nbanks, Dt, dqueries is not None)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    else:
+        _chk(workspace, torch.uint8, "workspace")
+        if workspace.numel() < need:
+            raise ValueError(f"class_logits_bwd: workspace must hold {need} bytes (class_logits_bwd_workspace_bytes), got {workspace.numel()}")
+    _lib.call("owl_class_logits_bwd", stream(), dlogits, e, queries, w_shift, w_scale, rowstats, mask, workspace, need, de, dfeats, dqueries,
+              B, P, Q, nbanks, (B if mask.dim() == 2 else 1) if mask is not None else 1, Dt, D)
+    return de, dfeats, dqueries
 
 
 def box_final(h, w2, b2, box_bias, boxes, sig, rows, P, D):
