@@ -3,8 +3,10 @@
  *
  * The reference (stevebottos/owl-vit-object-detection) has NO native layer: its hot path is Python
  * over stock aten kernels.  The drop-in boundary is therefore the Python
- * call surface (`model(image)`, `PushPullLoss(...)`, `HungarianMatcher(...)`); this header is the
- * thin C ABI underneath it.  Each entry point names the reference arithmetic it replaces
+ * call surface (`model(image)`, `PushPullLoss(...)`, `HungarianMatcher(...)`; for the open-vocabulary
+ * path `model.forward_queries(...)`, `OpenVocabLoss(...)`, `OpenVocabMatcher(...)`, whose contract is
+ * transformers' Deformable-DETR criterion, `TF:` = transformers/loss/loss_deformable_detr.py); this
+ * header is the thin C ABI underneath it.  Each entry point names the reference arithmetic it replaces
  * (`ref:` = path under the reference repo, `HF5:` = transformers/models/owlvit/modeling_owlvit.py).
  *
  * Conventions:
@@ -32,7 +34,7 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's); still 8, additive again: + owl_gemm_nt_plan and the OWL_GEMM_KERNEL_* ids (which kernels a GEMM call launches; host query); still 8, additive again: + owl_prefix_emit, owl_prefix_gather (the frozen-prefix activation cache); still 8, additive again: + owl_image_query_workspace_bytes, owl_image_query_select, owl_query_bank_fill (the query bank from image exemplars).  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's); still 8, additive again: + owl_gemm_nt_plan and the OWL_GEMM_KERNEL_* ids (which kernels a GEMM call launches; host query); still 8, additive again: + owl_prefix_emit, owl_prefix_gather (the frozen-prefix activation cache); still 8, additive again: + owl_image_query_workspace_bytes, owl_image_query_select, owl_query_bank_fill (the query bank from image exemplars); still 8, additive again: + owl_focal_match_cost, owl_focal_loss_workspace_bytes, owl_focal_loss_fwd, owl_box_pair_loss, owl_open_vocab_loss_reduce, owl_focal_loss_bwd, owl_box_pair_loss_bwd (the open-vocabulary criterion over [B, P, Q] logits).  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
 #define OWL_ABI_VERSION 8
 const char* owl_last_error(void);
@@ -425,6 +427,35 @@ int owl_class_logits_fwd(void* stream, const float* e, const float* queries, con
  *   irrelevant.  Limits: the forward's (1 <= Q <= 4096, Dt % 64 == 0, Dt <= 1024, D % 8 == 0, 1 <= P <= 8192); w_shift, w_scale, dfeats 16-byte aligned. */
 int owl_class_logits_bwd_workspace_bytes(int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t Dt, int want_dq, int64_t* bytes);
 int owl_class_logits_bwd(void* stream, const float* dlogits, const float* e, const float* queries, const float* w_shift, const float* w_scale, const float* rowstats, const unsigned char* mask, void* workspace, int64_t workspace_bytes, void* de_bf16, float* dfeats, float* dqueries, int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t nmasks, int64_t Dt, int64_t D);
+
+/* ---- open-vocabulary criterion (still ABI 8: additive; csrc/open_vocab_loss.hip, losses.OpenVocabLoss / matcher.OpenVocabMatcher) -------------------
+ * The DETR-family bipartite loss with sigmoid focal classification over the logits of owl_class_logits_fwd: transformers' DeformableDetrHungarianMatcher
+ * and DeformableDetrImageLoss(losses = labels, boxes) on (logits, corners_to_center(boxes)), for per-image query lists.  Shared operands:
+ *   logits f32 [B, P, Q] (-FLT_MAX under the mask); mask u8 [nmasks, Q], nmasks = B or 1, NULL = every query valid; boxes f32 [B, P, 4] corners;
+ *   labels i64 [B, Nmax], tgt_boxes f32 [B, Nmax, 4] corners, counts i32 [B] (matcher.PackedTargets; counts[b] = 0 is legal); a label indexes the image's
+ *   own query list, 0 <= label < Q.  Centre forms are taken inside the kernels: cx = (x0 + x1) / 2, w = x1 - x0; gradients come back on the corners.
+ *   owl_focal_match_cost   costT f32 [B, Nmax, P] (owl_hungarian's layout; rows j >= counts[b] are not written), with p = sigmoid(logits[b, p, label_j]):
+ *       w_bbox L1(centre forms) + w_class (alpha (1 - p)^2 (-log(p + 1e-8)) - (1 - alpha) p^2 (-log(1 - p + 1e-8))) + w_giou (-GIoU(corners)).
+ *       A label outside [0, Q) or on a masked query never indexes the logits: class term 0 here, loss_ce NaN below.  Then owl_hungarian with bg = Q.
+ *   owl_focal_loss_fwd     one f64 partial per workgroup of sum over (b, p, live q) of alpha_t softplus(z) sigmoid(z)^2, z = t ? -x : x,
+ *       t = (target_classes[b, p] == q): HF's sigmoid_focal_loss term at gamma = 2, with 1 - p_t evaluated as sigmoid(z).  alpha < 0: no alpha weighting.
+ *       Reads the logits once, 16 bytes per lane where Q % 4 == 0 (logits 16-byte aligned then).  Masked columns are selected out, never multiplied.
+ *   owl_box_pair_loss      per image, over the matched pairs (pred_idx, tgt_idx i64 [B, Nmax] of owl_hungarian): sum L1 on centre forms, sum 1 - GIoU, and
+ *       the unscaled gradients dl1, dgiou f32 [B, P, 4] wrt the corners, zero on unmatched rows (both NULL: not formed); torch's tie and sign(0) conventions.
+ *   owl_open_vocab_loss_reduce   losses f32 [3] = (loss_ce, loss_bbox, loss_giou) = the three sums / num_boxes, partials added in one fixed order.
+ *   owl_focal_loss_bwd     dlogits f32 [B, P, Q] = (g3[0] / num_boxes) d element / dx, recomputed from x and t; exactly +0.0 under the mask; reads the logits
+ *       once and writes dlogits once.  g3 f32 [3] on the DEVICE = the upstream gradients of the three losses.
+ *   owl_box_pair_loss_bwd  dboxes f32 [B, P, 4] = (g3[1] dl1 + g3[2] dgiou) / num_boxes.
+ *   workspace: owl_focal_loss_workspace_bytes(B, P, Q), 8-byte aligned, written by owl_focal_loss_fwd and owl_box_pair_loss, read by the reduce.
+ *   num_boxes: a positive HOST double.  Sums are f64 (thread, wave butterfly, workgroup partial); no atomics, nothing allocated, no host sync; every
+ *   summation order is a function of (B, P, Q) alone: two runs give equal bits.  1 <= Q <= 4096, 1 <= P <= 8192, 1 <= Nmax <= P, B P < 2^31.             */
+int owl_focal_match_cost(void* stream, const float* logits, const unsigned char* mask, const float* boxes, const int64_t* labels, const float* tgt_boxes, const int* counts, float* costT, int64_t B, int64_t P, int64_t Q, int64_t nmasks, int64_t Nmax, float alpha, float w_class, float w_bbox, float w_giou);
+int owl_focal_loss_workspace_bytes(int64_t B, int64_t P, int64_t Q, int64_t* bytes);
+int owl_focal_loss_fwd(void* stream, const float* logits, const unsigned char* mask, const int64_t* target_classes, void* workspace, int64_t workspace_bytes, int64_t B, int64_t P, int64_t Q, int64_t nmasks, float alpha);
+int owl_box_pair_loss(void* stream, const float* boxes, const unsigned char* mask, const int64_t* labels, const float* tgt_boxes, const int64_t* pred_idx, const int64_t* tgt_idx, const int* counts, void* workspace, int64_t workspace_bytes, float* dl1, float* dgiou, int64_t B, int64_t P, int64_t Q, int64_t nmasks, int64_t Nmax);
+int owl_open_vocab_loss_reduce(void* stream, const void* workspace, int64_t workspace_bytes, float* losses, int64_t B, int64_t P, int64_t Q, double num_boxes);
+int owl_focal_loss_bwd(void* stream, const float* g3, const float* logits, const unsigned char* mask, const int64_t* target_classes, float* dlogits, int64_t B, int64_t P, int64_t Q, int64_t nmasks, float alpha, double num_boxes);
+int owl_box_pair_loss_bwd(void* stream, const float* g3, const float* dl1, const float* dgiou, float* dboxes, int64_t B, int64_t P, double num_boxes);
 
 /* ---- utilities ------------------------------------------------------------------------------------ */
 int owl_cast_f32_bf16(void* stream, const float* in, void* out, int64_t n);

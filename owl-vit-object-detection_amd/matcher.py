@@ -40,17 +40,20 @@ class PackedTargets:
     Host tensors are packed on the host into ONE pinned staging buffer and cross PCIe in ONE async copy; device tensors are
     concatenated and padded by one kernel (owl_pack_targets) -- never B small copies.  `n_classes` (optional) validates the
     label range where the labels are still host tensors (the reference raises IndexError for such a label, src/matcher.py:118);
-    for device-resident labels the kernels refuse to index with a bad label and poison loss_ce with NaN instead."""
+    for device-resident labels the kernels refuse to index with a bad label and poison loss_ce with NaN instead.
 
-    def __init__(self, labels, boxes, device, n_classes=None):
+    `allow_empty=True` (the open-vocabulary criterion, where an image without targets is a pure negative) admits images with no target:
+    Nmax = max(1, max(sizes)), their rows all padding and their count 0.  The default keeps the error."""
+
+    def __init__(self, labels, boxes, device, n_classes=None, allow_empty=False):
         labels, boxes = list(labels), list(boxes)
         sizes = [int(l.shape[0]) for l in labels]
         if any(int(b.shape[0]) != n for b, n in zip(boxes, sizes)):
             raise ValueError("labels / boxes length mismatch")
-        if not sizes or min(sizes) < 1:
+        if not sizes or (min(sizes) < 1 and not allow_empty):
             raise ValueError("every image needs at least one target box (the reference drops empty images, src/dataset.py:33)")
         device = torch.device(device)
-        B, Nmax = len(sizes), max(sizes)
+        B, Nmax = len(sizes), max(1, max(sizes))
         self.sizes, self.Nmax = sizes, Nmax
         nl, nb = B * Nmax * 8, B * Nmax * 16
         on_host = all(not t.is_cuda for t in labels) and all(not t.is_cuda for t in boxes)
@@ -63,6 +66,8 @@ class PackedTargets:
                 self.labels = torch.zeros(B, Nmax, dtype=torch.int64)
                 self.boxes = torch.zeros(B, Nmax, 4, dtype=torch.float32)
                 for b, (l, bx) in enumerate(zip(labels, boxes)):
+                    if not sizes[b]:
+                        continue
                     self.labels[b, : sizes[b]] = l.to(torch.int64)
                     self.boxes[b, : sizes[b]] = bx.to(torch.float32)
                 self.counts = torch.tensor(sizes, dtype=torch.int32)
@@ -74,9 +79,10 @@ class PackedTargets:
             hb = host[nl: nl + nb].view(torch.float32).view(B, Nmax, 4)
             hc = host[nl + nb: nl + nb + 4 * B].view(torch.int32)
             for b, (l, bx) in enumerate(zip(labels, boxes)):
-                hl[b, : sizes[b]] = l
-                hb[b, : sizes[b]] = bx
                 hc[b] = sizes[b]
+                if sizes[b]:
+                    hl[b, : sizes[b]] = l
+                    hb[b, : sizes[b]] = bx
             dev = torch.empty(nl + nb + 4 * B, dtype=torch.uint8, device=device)
             # (copy and event on `device`'s current stream -- which need not be the current device's)
             with torch.cuda.device(device):
@@ -86,6 +92,11 @@ class PackedTargets:
             self.labels = dev[:nl].view(torch.int64).view(B, Nmax)
             self.boxes = dev[nl: nl + nb].view(torch.float32).view(B, Nmax, 4)
             self.counts = dev[nl + nb:].view(torch.int32)
+            return
+        if sum(sizes) == 0:                         # (allow_empty, no target in the whole batch: all padding, nothing to concatenate)
+            self.labels = torch.zeros(B, Nmax, dtype=torch.int64, device=device)
+            self.boxes = torch.zeros(B, Nmax, 4, dtype=torch.float32, device=device)
+            self.counts = torch.zeros(B, dtype=torch.int32, device=device)
             return
         # device-resident lists (ref main.py:78-79 moves them with .to(device) before the criterion): concat + one pad kernel
         lab_cat = torch.cat([l.to(device=device, dtype=torch.int64).reshape(-1) for l in labels])
@@ -178,3 +189,86 @@ class HungarianMatcher(nn.Module):
         tc, pred_idx, tgt_idx, _ = self.match_packed(outputs["pred_logits"], outputs["pred_boxes"], tg)
         indices = [(pred_idx[b, :n], tgt_idx[b, :n]) for b, n in enumerate(tg.sizes)]
         return tc, indices, self._get_src_permutation_idx(indices)
+
+
+def pack_open_vocab_targets(targets, device, Q=None, query_mask=None, box_format="xyxy"):
+    """The open-vocabulary criterion's targets -> PackedTargets (allow_empty): a list of {"class_labels" | "labels", "boxes"} per image, a label an index
+    into that image's own query list.  `box_format`: "xyxy" corners (what the model predicts), or "cxcywh" (HF's target form), converted ONCE here.
+    Host-resident labels are validated on the host: a label outside [0, Q) raises IndexError, and so does one that points at a masked query where the
+    mask is a host tensor too (device-resident labels, or a device mask: the kernels poison loss_ce with NaN instead, no sync)."""
+    if isinstance(targets, PackedTargets):
+        return targets
+    if box_format not in ("xyxy", "cxcywh"):
+        raise ValueError(f"box_format must be 'xyxy' or 'cxcywh', got {box_format!r}")
+    labels = [t["class_labels"] if "class_labels" in t else t["labels"] for t in targets]
+    boxes = [t["boxes"].reshape(-1, 4) for t in targets]
+    if box_format == "cxcywh":
+        boxes = [torch.cat([b[:, :2] - 0.5 * b[:, 2:], b[:, :2] + 0.5 * b[:, 2:]], dim=-1) for b in boxes]
+    host_mask = query_mask is not None and not query_mask.is_cuda
+    for i, l in enumerate(labels):
+        if l.is_cuda or not l.numel():
+            continue
+        if Q is not None and (int(l.min()) < 0 or int(l.max()) >= Q):
+            raise IndexError(f"target label outside [0, {Q}) on image {i}")
+        if host_mask:
+            row = query_mask if query_mask.dim() == 1 else query_mask[0 if query_mask.shape[0] == 1 else i]
+            if not bool(row.bool()[l.long()].all()):
+                raise IndexError(f"target label on image {i} points at a masked query")
+    return PackedTargets(labels, boxes, device, None, allow_empty=True)
+
+
+def _mask_u8(query_mask, B, Q, device):
+    """query_mask [B, Q] / [1, Q] / [Q] (bool or integer, nonzero = valid) or None -> (u8 device tensor or None, nmasks)."""
+    if query_mask is None:
+        return None, 1
+    m = query_mask.reshape(1, -1) if query_mask.dim() == 1 else query_mask
+    if m.dim() != 2 or m.shape[1] != Q or m.shape[0] not in (1, B):
+        raise ValueError(f"query_mask must be [B, Q], [1, Q] or [Q] with B={B}, Q={Q}; got {tuple(query_mask.shape)}")
+    return (m != 0).to(device=device, dtype=torch.uint8).contiguous(), int(m.shape[0])
+
+
+class OpenVocabMatcher(nn.Module):
+    """Bipartite matcher for the [B, P, Q] logits of `OwlViT.forward_queries` / `forward_text`: transformers' DeformableDetrHungarianMatcher (sigmoid focal
+    class cost with alpha = 0.25 and gamma = 2, L1 on centre forms, GIoU) on (logits, corners_to_center(pred_boxes)), on device with no host sync
+    (csrc/open_vocab_loss.hip: owl_focal_match_cost; the assignment solve is loss.hip's owl_hungarian, unchanged).  The cost defaults are
+    DeformableDetrConfig's (class_cost 1, bbox_cost 5, giou_cost 2).  Returns HungarianMatcher.forward's structure."""
+
+    def __init__(self, class_cost: float = 1, bbox_cost: float = 5, giou_cost: float = 2, alpha: float = 0.25):
+        super().__init__()
+        if class_cost == 0 and bbox_cost == 0 and giou_cost == 0:
+            raise ValueError("all costs cant be 0")
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError("the matcher's alpha must lie in [0, 1]")
+        self.class_cost, self.bbox_cost, self.giou_cost, self.alpha = class_cost, bbox_cost, giou_cost, alpha
+
+    @torch.no_grad()
+    def match_packed(self, logits, pred_boxes, tg: PackedTargets, mask_u8=None, nmasks=1):
+        """Device-only core: returns (target_classes [B,P] i64 with background = Q, pred_idx [B,Nmax] i64, tgt_idx [B,Nmax] i64, costT [B,Nmax,P])."""
+        B, P, Q = logits.shape
+        dev = logits.device
+        if tg.Nmax > P:
+            raise ValueError("more targets than predictions is not supported")
+        if len(tg.sizes) != B:
+            raise ValueError("batch size mismatch between predictions and targets")
+        lg = logits.detach().contiguous().float()
+        boxes = pred_boxes.detach().contiguous().float()
+        costT = torch.empty(B, tg.Nmax, P, dtype=torch.float32, device=dev)
+        pred_idx = torch.empty(B, tg.Nmax, dtype=torch.int64, device=dev)
+        tgt_idx = torch.empty(B, tg.Nmax, dtype=torch.int64, device=dev)
+        tc = torch.empty(B, P, dtype=torch.int64, device=dev)
+        s = ops.stream()
+        _lib.call("owl_focal_match_cost", s, lg, mask_u8, boxes, tg.labels, tg.boxes, tg.counts, costT, B, P, Q, nmasks, tg.Nmax,
+                  float(self.alpha), float(self.class_cost), float(self.bbox_cost), float(self.giou_cost))
+        _lib.call("owl_hungarian", s, costT, tg.labels, tg.counts, pred_idx, tgt_idx, tc, B, P, tg.Nmax, Q)
+        return tc, pred_idx, tgt_idx, costT
+
+    @torch.no_grad()
+    def forward(self, outputs, targets, query_mask=None, box_format="xyxy"):
+        """outputs: {"logits" | "pred_logits": [B, P, Q], "pred_boxes": [B, P, 4] corners}; returns (target_classes, indices, idx)."""
+        logits = outputs["logits"] if "logits" in outputs else outputs["pred_logits"]
+        B, P, Q = logits.shape
+        tg = pack_open_vocab_targets(targets, logits.device, Q, query_mask, box_format)
+        mask_u8, nmasks = _mask_u8(query_mask, B, Q, logits.device)
+        tc, pred_idx, tgt_idx, _ = self.match_packed(logits, outputs["pred_boxes"], tg, mask_u8, nmasks)
+        indices = [(pred_idx[b, :n], tgt_idx[b, :n]) for b, n in enumerate(tg.sizes)]
+        return tc, indices, HungarianMatcher._get_src_permutation_idx(indices)

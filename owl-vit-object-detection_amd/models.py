@@ -1033,7 +1033,8 @@ class OwlViT(nn.Module):
         gradient), the four logit-head tensors (frozen buffers; the gradient passes through them to the features) and any text tower.  If
         `query_embeds.requires_grad` it receives its gradient as an ordinary autograd gradient (prompt tuning: the tensor is the caller's, stepped by
         any torch optimizer; under the deferred tail the caller's stream is ordered behind it).  As with `forward`, call backward() before the next
-        recording forward at the same batch size (RuntimeError otherwise).  The loss over [B, P, Q] logits is the caller's torch code.
+        recording forward at the same batch size (RuntimeError otherwise).  The loss over [B, P, Q] logits is
+        `losses.OpenVocabLoss` (bipartite matching, sigmoid focal + L1 / GIoU, on device with no host sync), or any torch code of the caller's.
 
         Under no_grad it is `detect`."""
         if self.logit_head is None:
