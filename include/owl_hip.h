@@ -428,6 +428,24 @@ int owl_class_logits_fwd(void* stream, const float* e, const float* queries, con
 int owl_class_logits_bwd_workspace_bytes(int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t Dt, int want_dq, int64_t* bytes);
 int owl_class_logits_bwd(void* stream, const float* dlogits, const float* e, const float* queries, const float* w_shift, const float* w_scale, const float* rowstats, const unsigned char* mask, void* workspace, int64_t workspace_bytes, void* de_bf16, float* dfeats, float* dqueries, int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t nmasks, int64_t Dt, int64_t D);
 
+/* ---- open-vocabulary class head, backward with the gradients of the head's own tensors (still ABI 8: additive; csrc/open_vocab_bwd.hip) ---------------
+ * owl_class_logits_bwd plus the gradients of logit_shift / logit_scale (models.OwlViT.set_logit_head(head, trainable=True)).  Every operand and output of
+ * owl_class_logits_bwd means what it means there and carries the same bits; in addition
+ *     feats bf16 [B P, D]: the features the forward read (16-byte aligned);  rowgrad f32 [B P, 2]: caller's scratch (8-byte aligned), (dshift_r, ds_r)
+ *     of every row afterwards -- the row pass stores the two scalars it multiplies into dfeats; rows >= B P are not written
+ *     dw_shift[c] = sum_r dshift_r feats[r, c]    db_shift = sum_r dshift_r    dw_scale[c] = sum_r ds_r feats[r, c]    db_scale = sum_r ds_r
+ *     dw_shift / dw_scale f32 [D], db_shift / db_scale f32 [1]: plain stores, r over all B P rows.  dfeats and dqueries may be NULL as before: the four
+ *     gradients keep their bits.
+ *   Two more launches.  The first: one workgroup per (image, chunk of 256 rows, block of 128 columns), 16 row lanes x 16 column lanes, a thread reads 8
+ *   bf16 features (16 bytes) per row and adds dshift f and ds f in FLOAT64 -- a bf16 times an f32 is exact there, so only the adds round -- and writes one
+ *   f64 partial per workgroup into the workspace.  The second adds an image's partials in chunk order, then the images' sums in image order, and
+ *   rounds ONCE to f32.  No atomics, nothing allocated, no host sync; the chunking depends on nothing (256 rows), so an image's partials carry the same
+ *   bits wherever the image stands and two runs give equal bits.  Rows >= B P of feats and rowgrad are never read.
+ *   workspace: owl_class_logits_bwd_head_workspace_bytes(..., want_dq = dqueries != NULL) = owl_class_logits_bwd's plus 8 B ceil(P / 256) (2 D + 2) bytes.
+ *   Limits: owl_class_logits_bwd's, and D <= 2^20.                                                                                                      */
+int owl_class_logits_bwd_head_workspace_bytes(int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t Dt, int64_t D, int want_dq, int64_t* bytes);
+int owl_class_logits_bwd_head(void* stream, const float* dlogits, const float* e, const float* queries, const void* feats_bf16, const float* w_shift, const float* w_scale, const float* rowstats, const unsigned char* mask, void* workspace, int64_t workspace_bytes, float* rowgrad, void* de_bf16, float* dfeats, float* dqueries, float* dw_shift, float* dw_scale, float* db_shift, float* db_scale, int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t nmasks, int64_t Dt, int64_t D);
+
 /* ---- open-vocabulary criterion (still ABI 8: additive; csrc/open_vocab_loss.hip, losses.OpenVocabLoss / matcher.OpenVocabMatcher) -------------------
  * The DETR-family bipartite loss with sigmoid focal classification over the logits of owl_class_logits_fwd: transformers' DeformableDetrHungarianMatcher
  * and DeformableDetrImageLoss(losses = labels, boxes) on (logits, corners_to_center(boxes)), for per-image query lists.  Shared operands:

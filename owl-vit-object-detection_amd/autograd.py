@@ -92,7 +92,8 @@ class OwlViTFunction(torch.autograd.Function):
 class OwlViTQueryFunction(torch.autograd.Function):
     """models.OwlViT.forward_queries with grad enabled: the same forward, HF's class head (ops.class_logits) over the caller's per-image queries on the
     training workspace's e / feats, and backward_impl with the class-head adjoint switched to ops.class_logits_bwd.  The learnable bank takes no part;
-    `query_embeds` receives its gradient as an ordinary autograd gradient when it requires one."""
+    `query_embeds` receives its gradient as an ordinary autograd gradient when it requires one, and so do the four leaves of a trainable logit head
+    (models.OwlViT.set_logit_head(head, trainable=True)): they follow the bucket's parameters as explicit inputs, in weights.LOGIT_HEAD_KEYS' order."""
 
     @staticmethod
     def forward(ctx, model, image, query_embeds, query_mask, *params):
@@ -102,6 +103,7 @@ class OwlViTQueryFunction(torch.autograd.Function):
         ctx.model, ctx.B = model, B
         ctx.gen = model._workspace(B)["gen"]
         ctx.qe, ctx.qm = query_embeds.detach(), query_mask
+        ctx.n_head = len(params) - len(model.flat_offsets)          # 4: a trainable logit head's leaves; 0: the frozen head, today's launches
         return boxes, logits
 
     @staticmethod
@@ -113,25 +115,32 @@ class OwlViTQueryFunction(torch.autograd.Function):
                 "forward at the same batch size (or evicted: only the model's `max_cached_batch_sizes` most recent batch sizes keep their "
                 "workspaces); call backward() before the next training forward (no-grad / eval forwards are fine)")
         dq = torch.empty_like(ctx.qe) if ctx.needs_input_grad[2] else None
-        head = dict(dlogits=d_logits, queries=ctx.qe, mask=ctx.qm, dq=dq, event=None)
+        D, nflat = model.cfg.hidden, len(model.flat_offsets)
+        dhead = None
+        if ctx.n_head and any(ctx.needs_input_grad[4 + nflat:]):
+            dhead = torch.empty(2 * D + 2, dtype=torch.float32, device=d_logits.device)          # w_shift | w_scale | b_shift | b_scale
+        head = dict(dlogits=d_logits, queries=ctx.qe, mask=ctx.qm, dq=dq, dhead=dhead, event=None)
         if getattr(model, "overlap_tail", False) and d_boxes.is_cuda:
             main, ts = torch.cuda.current_stream(), model._tail_stream
             ts.wait_stream(main)
-            for t in (d_boxes, d_logits, ctx.qe, ctx.qm, dq):
+            for t in (d_boxes, d_logits, ctx.qe, ctx.qm, dq, dhead):
                 if t is not None:
                     t.record_stream(ts)           # (allocated on the compute stream, used on the tail stream)
             with torch.cuda.stream(ts):
-                if dq is not None:
-                    head["event"] = torch.cuda.Event()          # recorded where the query gradient is complete, not at the tail's end
+                if dq is not None or dhead is not None:
+                    head["event"] = torch.cuda.Event()          # recorded where the query and logit-head gradients are complete, not at the tail's end
                 backward_impl(model, B, d_boxes, None, None, logit_head=head)
                 ev = torch.cuda.Event()
                 ev.record(ts)
             model._param_event = ev
-            if dq is not None:
-                main.wait_event(head["event"])    # the query gradient goes back to the caller's stream: ordered here
+            if head["event"] is not None:
+                main.wait_event(head["event"])    # the query and logit-head gradients go back to the caller's stream: ordered here
         else:
             backward_impl(model, B, d_boxes, None, None, logit_head=head)
-        return (None, None, dq, None) + (None,) * len(model.flat_offsets)
+        hg = (None,) * ctx.n_head
+        if dhead is not None:          # (weights.LOGIT_HEAD_KEYS' order: shift.weight, shift.bias, scale.weight, scale.bias)
+            hg = (dhead[:D], dhead[2 * D:2 * D + 1], dhead[D:2 * D], dhead[2 * D + 1:])
+        return (None, None, dq, None) + (None,) * nflat + hg
 
 
 def _bws(model, B):
@@ -291,10 +300,12 @@ def patch_weight_grad(dE, patches, grad_w, D, K, rows, scratch=None, accumulate=
 
 
 def backward_impl(model, B, d_boxes, d_sims, sims, logit_head=None):
-    """logit_head (None = the bank head's adjoint, today's launches): dict(dlogits [B, P, Q], queries, mask, dq, event) -- the class-head section is then
+    """logit_head (None = the bank head's adjoint, today's launches): dict(dlogits [B, P, Q], queries, mask, dq, dhead, event) -- the class-head section is then
     the adjoint of ops.class_logits (OwlViTQueryFunction): class_logits_bwd writes de and the shift / scale part of d(feats), dense0's dW runs as ever,
     its dX GEMM ACCUMULATES into d(feats), then the box head's does: one fixed order of the three contributions.  `dq` (or None) receives the query
-    gradient and `event` (or None) is recorded on the calling stream once it is complete.  d_sims / sims are not read."""
+    gradient, `dhead` (or None: a frozen logit head, today's launches) the f32 [2 D + 2] gradients of logit_shift / logit_scale -- two more launches in
+    the class-head section, on its stream, also where the floor forms no d(feats) -- and `event` (or None) is recorded on the calling stream once both
+    are complete.  d_sims / sims are not read."""
     cfg = model.cfg
     D, I, H, Tp, T, P, Dt, C = cfg.hidden, cfg.mlp, cfg.heads, cfg.tokens_padded, cfg.tokens, cfg.patches, cfg.text_dim, cfg.n_classes
     M, Mh = B * Tp, B * P
@@ -352,15 +363,22 @@ def backward_impl(model, B, d_boxes, d_sims, sims, logit_head=None):
     with torch.cuda.stream(hs):
         if logit_head is not None:
             # HF's class head over the caller's queries (csrc/open_vocab_bwd.hip); the learnable bank takes no part
-            dq = logit_head["dq"]
-            if t_cls or below_heads or dq is not None:
+            dq, dhead = logit_head["dq"], logit_head.get("dhead")
+            if t_cls or below_heads or dq is not None or dhead is not None:
                 lh, qe, qm = model.logit_head, logit_head["queries"], logit_head["mask"]
                 nbanks = B if qe.dim() == 3 else 1
-                key, need = "ovb", ops.class_logits_bwd_workspace_bytes(B, P, qe.shape[-2], nbanks, Dt, dq is not None)
+                if dhead is None:
+                    key, need, more = "ovb", ops.class_logits_bwd_workspace_bytes(B, P, qe.shape[-2], nbanks, Dt, dq is not None), {}
+                else:          # the head trains: the same launches, the row pass also stores (dshift, ds) per row, two more launches reduce them
+                    key, need = "ovb", ops.class_logits_bwd_head_workspace_bytes(B, P, qe.shape[-2], nbanks, Dt, D, dq is not None)
+                    if "ovb_rowgrad" not in bw:
+                        bw["ovb_rowgrad"] = torch.zeros(Mh, 2, dtype=torch.float32, device=model.device_)
+                    more = dict(feats=ws["feats"], dhead=dhead, rowgrad=bw["ovb_rowgrad"])
                 if key not in bw or bw[key].numel() < need:          # (one buffer per batch size, grown to the largest query count seen)
                     bw[key] = torch.empty(need, dtype=torch.uint8, device=model.device_)
-                ops.class_logits_bwd(d_logits, ws["e"], qe, lh["logit_shift.weight"], lh["logit_scale.weight"], ws["logit_rowstats"], B, P, mask=qm,
-                                     de=bw["de"], dfeats=bw["dfeats"] if below_heads else False, dqueries=dq if dq is not None else False, workspace=bw[key])
+                ops.class_logits_bwd(d_logits, ws["e"], qe, lh["logit_shift.weight"].detach(), lh["logit_scale.weight"].detach(), ws["logit_rowstats"], B, P,
+                                     mask=qm, de=bw["de"], dfeats=bw["dfeats"] if below_heads else False, dqueries=dq if dq is not None else False,
+                                     workspace=bw[key], **more)
                 if t_cls:
                     weight_grad(bw["de"], ws["feats"], G("class_predictor.dense0.weight"), Dt, D, Mh, cdw, G("class_predictor.dense0.bias"))
                 if below_heads:

@@ -30,7 +30,8 @@ for f in $SRCS; do
       # (open_vocab.hip: the order of its row norm, add and multiply is the one tests/open_vocab_reference.py bounds; its dot products name their FMAs)
       # (color_jitter.hip: Pillow's Image.blend rounds the product and the sum separately, tests/color_reference.py; a fused multiply-add is not Pillow's bits)
       # (slice_merge.hip: the slice -> image map is a multiply then an add, and its overlap chain is postprocess.hip's, tests/slice_merge_reference.py)
-      # (open_vocab_bwd.hip: tests/open_vocab_bwd_reference.py counts one rounding per written operation of the row scalars, de, dfeats and dq)
+      # (open_vocab_bwd.hip: tests/open_vocab_bwd_reference.py counts one rounding per written operation of the row scalars, de, dfeats and dq;
+      #  tests/logit_head_grad_reference.py counts on exact f64 products and separately rounded f64 adds in the head-gradient sums)
       # (open_vocab_loss.hip: tests/open_vocab_loss_reference.py counts one rounding per written operation of the cost, the focal term and the box pairs)
       loss.hip|postprocess.hip|metrics.hip|pos_resample.hip|image_query.hip|open_vocab.hip|open_vocab_bwd.hip|open_vocab_loss.hip|color_jitter.hip|slice_merge.hip) extra="-ffp-contract=off";;
       # packed f32 VALU (v_pk_mul/add_f32) beside MFMAs costs more than the two scalar instructions it replaces

@@ -11,6 +11,14 @@
 // Compiled with contraction off (csrc/build.sh): every written operation rounds once, the count tests/open_vocab_bwd_reference.py bounds.  No atomics,
 // nothing allocated, no host sync; every sum has one fixed order that depends on (P, Q, Dt) alone, not on the batch: two runs give equal bits and an
 // image's block carries the same bits wherever it stands.
+//
+// Gradients of the head's own four tensors (owl_class_logits_bwd_head): the row pass also stores its (dshift_r, ds_r) into `rowgrad`, then
+//   dW_shift[c] = sum_r dshift_r feats[r, c]   db_shift = sum_r dshift_r   dW_scale[c] = sum_r ds_r feats[r, c]   db_scale = sum_r ds_r     (r over all B P rows)
+// in two launches (ovb_head_part_kernel, ovb_head_finish_kernel).  Accumulation is FLOAT64, one rounding to f32 at the final store: a bf16 feature times
+// an f32 row scalar is exact in f64 (8 x 24 significand bits), so the only roundings of the reduction are its f64 adds (2^-53 each) and the last
+// conversion.  The reason: the sum runs over B P rows (73 728 at B/16, batch 32) of terms that cancel, so an f32 chain's error would grow with the batch
+// and stand beside -- not under -- what dshift / ds inherit from the row pass; in f64 the bound is the inherited one plus half an f32 ulp at every batch
+// size.  It costs nothing: the pass is bound by the one read of feats, and gfx950's vector f64 adds run at half the f32 rate.
 #include "common.h"
 
 #define OVB_MAX_QUERIES 4096
@@ -45,7 +53,8 @@ template <int NT>
 __global__ __launch_bounds__(256) void ovb_rows_kernel(const float* __restrict__ dlogits, const float* __restrict__ e, const float* __restrict__ qhat,
                                                        const float* __restrict__ rowstats, const unsigned char* __restrict__ mask,
                                                        const float* __restrict__ w_shift, const float* __restrict__ w_scale, bf16_t* de, float* dfeats,
-                                                       float* rowfac, int P, int Q, int Qp, int Dt, int D, int nbanks, int nmasks, int tiles_img) {
+                                                       float* rowfac, float* rowgrad, int P, int Q, int Qp, int Dt, int D, int nbanks, int nmasks,
+                                                       int tiles_img) {
     __shared__ __attribute__((aligned(16))) float ga[32 * OVB_LD];
     __shared__ float s_gs[32], s_part[2][4][32], s_a[32], s_coef[32], s_dsh[32], s_ds[32];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hi = lane >> 5, l31 = lane & 31;
@@ -152,6 +161,7 @@ __global__ __launch_bounds__(256) void ovb_rows_kernel(const float* __restrict__
         s_dsh[i] = dshift;
         s_ds[i] = ds;
         if (i < nrows) rowfac[row] = a;
+        if (rowgrad && i < nrows) *(float2*)(rowgrad + row * 2) = make_float2(dshift, ds);          // (the head's own gradients: ovb_head_part_kernel)
     }
     __syncthreads();
 #pragma unroll
@@ -271,6 +281,103 @@ __global__ __launch_bounds__(64) void ovb_dq_finish_kernel(const float* __restri
     }
 }
 
+// ---- gradients of logit_shift / logit_scale: partial sums of one (image, chunk of OVB_HEAD_CHUNK rows, block of 128 columns) ------------------------
+// 256 threads = 16 row lanes x 16 column lanes; a thread owns 8 adjacent columns (one 16-byte load of bf16 features per row) and the rows
+// pbeg + rl, pbeg + rl + 16, ... of the chunk in ascending order.  A row of the block is 256 contiguous bytes, a wave reads four rows at once: at
+// D = 128 every lane of every wave has columns (a lane-per-8-columns layout ALONG the row would leave 48 lanes of a wave idle there).  The 16 row
+// lanes are then added in index order through LDS (the shift sums, then the scale sums, through one tile); column lane 0 also sums the two row scalars themselves (the bias gradients; block 0 stores them).
+// part[(b S + s)][2 D + 2] f64, laid out w_shift | w_scale | b_shift | b_scale.  The chunking is a constant: a function of nothing but the source.
+#define OVB_HEAD_CHUNK 256
+__global__ __launch_bounds__(256) void ovb_head_part_kernel(const bf16_t* __restrict__ feats, const float* __restrict__ rowgrad, double* part, int P, int D,
+                                                            int S, int ncb) {
+    __shared__ double s_acc[16][16][9];                 // [row lane][column lane][8 sums (+1: bank spread)]: the shift sums, then the scale sums
+    __shared__ double s_b[16][2];
+    const int tid = threadIdx.x, cl = tid & 15, rl = tid >> 4;
+    const int cb = blockIdx.x % ncb, s = (blockIdx.x / ncb) % S, b = blockIdx.x / (ncb * S);
+    const int pbeg = s * OVB_HEAD_CHUNK, pend = min(P, pbeg + OVB_HEAD_CHUNK);
+    const int c0 = cb * 128 + cl * 8;
+    const bool colok = c0 < D;                          // (D % 8 == 0: a thread's eight columns exist together)
+    double ash[8], asc[8], bsh = 0.0, bsc = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { ash[j] = 0.0; asc[j] = 0.0; }
+    if (colok) {
+#pragma unroll 4
+        for (int p = pbeg + rl; p < pend; p += 16) {
+            const int64_t row = (int64_t)b * P + p;
+            const uint4 v = *(const uint4*)(feats + row * D + c0);
+            const float2 g = *(const float2*)(rowgrad + row * 2);
+            const double gsh = (double)g.x, gsc = (double)g.y;
+            const unsigned wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const double f0 = (double)__uint_as_float(wd[j] << 16), f1 = (double)__uint_as_float(wd[j] & 0xffff0000u);
+                ash[2 * j] = ash[2 * j] + gsh * f0;
+                ash[2 * j + 1] = ash[2 * j + 1] + gsh * f1;
+                asc[2 * j] = asc[2 * j] + gsc * f0;
+                asc[2 * j + 1] = asc[2 * j + 1] + gsc * f1;
+            }
+            bsh = bsh + gsh;
+            bsc = bsc + gsc;
+        }
+    }
+    double* out = part + (int64_t)(b * S + s) * (2 * D + 2);
+    if (cl == 0) { s_b[rl][0] = bsh; s_b[rl][1] = bsc; }
+#pragma unroll
+    for (int which = 0; which < 2; which++) {           // (two rounds through an LDS tile of half the size: eight workgroups fit a CU, not four)
+        if (which) __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 8; j++) s_acc[rl][cl][j] = which ? asc[j] : ash[j];
+        __syncthreads();
+        const int c = tid;                              // one of the block's 128 columns per thread
+        if (c < 128 && cb * 128 + c < D) {
+            double t = 0.0;
+#pragma unroll
+            for (int r = 0; r < 16; r++) t = t + s_acc[r][c >> 3][c & 7];
+            out[(int64_t)which * D + cb * 128 + c] = t;
+        }
+    }
+    if (cb == 0 && tid < 2) {
+        double t = 0.0;
+#pragma unroll
+        for (int r = 0; r < 16; r++) t = t + s_b[r][tid];
+        out[2 * D + tid] = t;
+    }
+}
+
+// ---- the partials of an image added in chunk order, then the images' sums in image order, ONE rounding to f32 ---------------------------------------
+// A workgroup owns 32 adjacent outputs (256 contiguous bytes of every partial); its 8 image lanes each add the S chunks of one image of a tile of
+// eight, the eight sums go through LDS and image lane 0 adds them to the running total in ascending order.  (One thread per output over all B S
+// partials is the same sum in a chain of B S dependent loads: 74 us at B S = 288, twice the partial-sum launch.)
+__global__ __launch_bounds__(256) void ovb_head_finish_kernel(const double* __restrict__ part, float* dw_shift, float* dw_scale, float* db_shift,
+                                                              float* db_scale, int D, int B, int S) {
+    __shared__ double s_img[8][32];
+    const int ol = threadIdx.x & 31, il = threadIdx.x >> 5;
+    const int n = 2 * D + 2, o = blockIdx.x * 32 + ol;
+    double tot = 0.0;
+    for (int b0 = 0; b0 < B; b0 += 8) {                 // (block-uniform trip count: the barriers are reached by every thread)
+        const int b = b0 + il;
+        double t = 0.0;
+        if (b < B && o < n) {
+            const double* p = part + (int64_t)b * S * n + o;
+#pragma unroll 4
+            for (int s = 0; s < S; s++) t = t + p[(int64_t)s * n];
+        }
+        s_img[il][ol] = t;
+        __syncthreads();
+        if (il == 0) {
+            const int nb = min(8, B - b0);
+            for (int i = 0; i < nb; i++) tot = tot + s_img[i][ol];
+        }
+        __syncthreads();
+    }
+    if (il != 0 || o >= n) return;
+    const float v = (float)tot;
+    if (o < D) dw_shift[o] = v;
+    else if (o < 2 * D) dw_scale[o - D] = v;
+    else if (o == 2 * D) db_shift[0] = v;
+    else db_scale[0] = v;
+}
+
 // rows of one dq^ partial slab: the image's rows in at most max(1, 64 / query blocks) chunks of a multiple of 32 rows -- a function of (P, Q) alone
 static void ovb_split(int64_t P, int64_t Q, int* S, int* chunk) {
     const int nqb = (int)((Q + 31) / 32);
@@ -304,24 +411,21 @@ OWL_API int owl_class_logits_bwd_workspace_bytes(int64_t B, int64_t P, int64_t Q
     return 0;
 }
 
-OWL_API int owl_class_logits_bwd(void* stream, const float* dlogits, const float* e, const float* queries, const float* w_shift, const float* w_scale,
-                                 const float* rowstats, const unsigned char* mask, void* workspace, int64_t workspace_bytes, void* de_bf16, float* dfeats,
-                                 float* dqueries, int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t nmasks, int64_t Dt, int64_t D) {
-    OWL_CHECK_ARG(dlogits && e && queries && w_shift && w_scale && rowstats && workspace && de_bf16, "owl_class_logits_bwd: null pointer");
-    if (ovb_check_shape("owl_class_logits_bwd", B, P, Q, nbanks, Dt)) return -1;
-    OWL_CHECK_ARG(D >= 8 && D % 8 == 0, "owl_class_logits_bwd: D %% 8 == 0 required (D=%lld)", (long long)D);
-    OWL_CHECK_ARG(!mask || nmasks == 1 || nmasks == B, "owl_class_logits_bwd: mask is [nmasks, Q] with nmasks = B or 1 (got %lld for B=%lld)", (long long)nmasks,
+// the launches of both entries; rowgrad (or null: owl_class_logits_bwd, whose launches and bits are what they were) receives (dshift, ds) per row
+static int ovb_launch(const char* who, void* stream, const float* dlogits, const float* e, const float* queries, const float* w_shift, const float* w_scale,
+                      const float* rowstats, const unsigned char* mask, void* workspace, void* de_bf16, float* dfeats, float* dqueries, float* rowgrad,
+                      int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t nmasks, int64_t Dt, int64_t D) {
+    OWL_CHECK_ARG(dlogits && e && queries && w_shift && w_scale && rowstats && workspace && de_bf16, "%s: null pointer", who);
+    if (ovb_check_shape(who, B, P, Q, nbanks, Dt)) return -1;
+    OWL_CHECK_ARG(D >= 8 && D % 8 == 0, "%s: D %% 8 == 0 required (D=%lld)", who, (long long)D);
+    OWL_CHECK_ARG(!mask || nmasks == 1 || nmasks == B, "%s: mask is [nmasks, Q] with nmasks = B or 1 (got %lld for B=%lld)", who, (long long)nmasks,
                   (long long)B);
     OWL_CHECK_ARG((((uintptr_t)w_shift | (uintptr_t)w_scale | (uintptr_t)dfeats | (uintptr_t)workspace) & 15) == 0 && ((uintptr_t)rowstats & 7) == 0,
-                  "owl_class_logits_bwd: w_shift, w_scale, dfeats and workspace must be 16-byte aligned, rowstats 8-byte aligned");
-    int64_t need = 0;
-    if (owl_class_logits_bwd_workspace_bytes(B, P, Q, nbanks, Dt, dqueries != nullptr, &need)) return -1;
-    OWL_CHECK_ARG(workspace_bytes >= need, "owl_class_logits_bwd: workspace of %lld bytes, %lld needed (owl_class_logits_bwd_workspace_bytes)",
-                  (long long)workspace_bytes, (long long)need);
+                  "%s: w_shift, w_scale, dfeats and workspace must be 16-byte aligned, rowstats 8-byte aligned", who);
     const int Qp = (int)((Q + 31) / 32 * 32), nqb = Qp / 32;
     int S, chunk;
     ovb_split(P, Q, &S, &chunk);
-    OWL_CHECK_ARG(B * S * nqb < ((int64_t)1 << 31), "owl_class_logits_bwd: B, P and Q together give too many workgroups for one launch");
+    OWL_CHECK_ARG(B * S * nqb < ((int64_t)1 << 31), "%s: B, P and Q together give too many workgroups for one launch", who);
     float* qhat = (float*)workspace;
     float* qnrm = qhat + nbanks * Qp * Dt;
     float* qinv = qnrm + ovb_align4(nbanks * Qp);
@@ -335,7 +439,7 @@ OWL_API int owl_class_logits_bwd(void* stream, const float* dlogits, const float
     const int per_wave = (int)((Dt / 32 + 3) / 4);
 #define OVB_ROWS(NT_)                                                                                                                              \
     hipLaunchKernelGGL(ovb_rows_kernel<NT_>, grid, dim3(256), 0, st, dlogits, e, qhat, rowstats, mask, w_shift, w_scale, (bf16_t*)de_bf16, dfeats, \
-                       rowfac, (int)P, (int)Q, Qp, (int)Dt, (int)D, (int)nbanks, (int)nmasks, tiles_img)
+                       rowfac, rowgrad, (int)P, (int)Q, Qp, (int)Dt, (int)D, (int)nbanks, (int)nmasks, tiles_img)
 #define OVB_DQ(NT_)                                                                                                                         \
     hipLaunchKernelGGL(ovb_dq_kernel<NT_>, dim3((unsigned)(B * S * nqb)), dim3(256), 0, st, dlogits, e, rowfac, mask, part, (int)P, (int)Q, Qp, \
                        (int)Dt, (int)nmasks, nqb, S, chunk)
@@ -356,6 +460,62 @@ OWL_API int owl_class_logits_bwd(void* stream, const float* dlogits, const float
 #undef OVB_DQ
     hipLaunchKernelGGL(ovb_dq_finish_kernel, dim3((unsigned)(nbanks * Q)), dim3(64), 0, st, part, queries, qhat, qnrm, qinv, dqueries, (int)Q, Qp, (int)Dt,
                        nbanks == 1 ? 0 : S, (int)(nbanks == 1 ? B * S : S));
+    OWL_LAUNCH_CHECK();
+    return 0;
+}
+
+OWL_API int owl_class_logits_bwd(void* stream, const float* dlogits, const float* e, const float* queries, const float* w_shift, const float* w_scale,
+                                 const float* rowstats, const unsigned char* mask, void* workspace, int64_t workspace_bytes, void* de_bf16, float* dfeats,
+                                 float* dqueries, int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t nmasks, int64_t Dt, int64_t D) {
+    OWL_CHECK_ARG(dlogits && e && queries && w_shift && w_scale && rowstats && workspace && de_bf16, "owl_class_logits_bwd: null pointer");
+    if (ovb_check_shape("owl_class_logits_bwd", B, P, Q, nbanks, Dt)) return -1;
+    OWL_CHECK_ARG(D >= 8 && D % 8 == 0, "owl_class_logits_bwd: D %% 8 == 0 required (D=%lld)", (long long)D);
+    int64_t need = 0;
+    if (owl_class_logits_bwd_workspace_bytes(B, P, Q, nbanks, Dt, dqueries != nullptr, &need)) return -1;
+    OWL_CHECK_ARG(workspace_bytes >= need, "owl_class_logits_bwd: workspace of %lld bytes, %lld needed (owl_class_logits_bwd_workspace_bytes)",
+                  (long long)workspace_bytes, (long long)need);
+    return ovb_launch("owl_class_logits_bwd", stream, dlogits, e, queries, w_shift, w_scale, rowstats, mask, workspace, de_bf16, dfeats, dqueries, nullptr, B, P,
+                      Q, nbanks, nmasks, Dt, D);
+}
+
+// workspace of owl_class_logits_bwd_head: owl_class_logits_bwd's, then the f64 partials [B S][2 D + 2] of the head gradients, S = ceil(P / OVB_HEAD_CHUNK)
+OWL_API int owl_class_logits_bwd_head_workspace_bytes(int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t Dt, int64_t D, int want_dq, int64_t* bytes) {
+    OWL_CHECK_ARG(bytes, "owl_class_logits_bwd_head_workspace_bytes: null pointer");
+    if (ovb_check_shape("owl_class_logits_bwd_head_workspace_bytes", B, P, Q, nbanks, Dt)) return -1;
+    OWL_CHECK_ARG(D >= 8 && D % 8 == 0 && D <= (1 << 20), "owl_class_logits_bwd_head_workspace_bytes: D %% 8 == 0 and D <= 2^20 required (D=%lld)", (long long)D);
+    int64_t base = 0;
+    if (owl_class_logits_bwd_workspace_bytes(B, P, Q, nbanks, Dt, want_dq, &base)) return -1;
+    const int64_t S = (P + OVB_HEAD_CHUNK - 1) / OVB_HEAD_CHUNK;
+    *bytes = base + 8 * B * S * (2 * D + 2);
+    return 0;
+}
+
+OWL_API int owl_class_logits_bwd_head(void* stream, const float* dlogits, const float* e, const float* queries, const void* feats_bf16, const float* w_shift,
+                                      const float* w_scale, const float* rowstats, const unsigned char* mask, void* workspace, int64_t workspace_bytes,
+                                      float* rowgrad, void* de_bf16, float* dfeats, float* dqueries, float* dw_shift, float* dw_scale, float* db_shift,
+                                      float* db_scale, int64_t B, int64_t P, int64_t Q, int64_t nbanks, int64_t nmasks, int64_t Dt, int64_t D) {
+    const char* who = "owl_class_logits_bwd_head";
+    OWL_CHECK_ARG(dlogits && e && queries && feats_bf16 && w_shift && w_scale && rowstats && workspace && rowgrad && de_bf16 && dw_shift && dw_scale && db_shift &&
+                      db_scale,
+                  "%s: null pointer", who);
+    int64_t need = 0, base = 0;
+    if (owl_class_logits_bwd_head_workspace_bytes(B, P, Q, nbanks, Dt, D, dqueries != nullptr, &need)) return -1;
+    if (owl_class_logits_bwd_workspace_bytes(B, P, Q, nbanks, Dt, dqueries != nullptr, &base)) return -1;
+    OWL_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed (owl_class_logits_bwd_head_workspace_bytes)", who,
+                  (long long)workspace_bytes, (long long)need);
+    OWL_CHECK_ARG(((uintptr_t)feats_bf16 & 15) == 0 && ((uintptr_t)rowgrad & 7) == 0, "%s: feats must be 16-byte aligned, rowgrad 8-byte aligned", who);
+    const int64_t S = (P + OVB_HEAD_CHUNK - 1) / OVB_HEAD_CHUNK, ncb = (D + 127) / 128;
+    OWL_CHECK_ARG(B * S * ncb < ((int64_t)1 << 31) && B * S < ((int64_t)1 << 31), "%s: B, P and D together give too many workgroups for one launch", who);
+    if (ovb_launch(who, stream, dlogits, e, queries, w_shift, w_scale, rowstats, mask, workspace, de_bf16, dfeats, dqueries, rowgrad, B, P, Q, nbanks, nmasks,
+                   Dt, D))
+        return -1;
+    double* part = (double*)((char*)workspace + base);          // (base is a multiple of 16)
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ovb_head_part_kernel, dim3((unsigned)(B * S * ncb)), dim3(256), 0, st, (const bf16_t*)feats_bf16, rowgrad, part, (int)P, (int)D, (int)S,
+                       (int)ncb);
+    OWL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ovb_head_finish_kernel, dim3((unsigned)((2 * D + 2 + 31) / 32)), dim3(256), 0, st, part, dw_shift, dw_scale, db_shift, db_scale, (int)D,
+                       (int)B, (int)S);
     OWL_LAUNCH_CHECK();
     return 0;
 }

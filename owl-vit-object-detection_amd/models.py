@@ -243,6 +243,7 @@ class OwlViT(nn.Module):
         # HF's class_head.logit_shift / logit_scale for zero-shot inference (detect): frozen device buffers outside flat_param, the parameter tree and
         # every state dict (plain attributes, as box_bias is); None until set_logit_head
         self.logit_head = None
+        self._logit_head_flat = None          # the one buffer behind a TRAINABLE head's four leaf views (set_logit_head(head, trainable=True))
 
     # -- module-tree plumbing -----------------------------------------------------------------------
     def _attach(self, dotted: str, p: nn.Parameter):
@@ -938,12 +939,20 @@ class OwlViT(nn.Module):
         return dict(box_indices=[h[0] for h in host], n_selected=[h[2] for h in host], fallback=[bool(h[1] & 1) for h in host], slots=table)
 
     # -- zero-shot inference: HF's class head over per-image text / image queries ---------------------------------------------
-    def set_logit_head(self, head):
+    def set_logit_head(self, head, trainable=False):
         """head: weights.hf_logit_head(sd) -- {"logit_shift.weight" [D], "logit_shift.bias" [], "logit_scale.weight" [D], "logit_scale.bias" []} (arrays
         or tensors).  They become frozen f32 device buffers in `model.logit_head`, outside flat_param, parameters() and state_dict(): nothing trains
-        through them and no checkpoint changes.  None removes them.  ValueError names a tensor of the wrong size, KeyError a missing one."""
+        through them and no checkpoint changes.  None removes them.  ValueError names a tensor of the wrong size, KeyError a missing one.
+
+        trainable=True: the four tensors live in ONE flat f32 device buffer of 2 D + 2 elements, laid out w_shift | w_scale | b_shift | b_scale, and
+        `model.logit_head` holds four leaf views of it with requires_grad=True (the same four keys: detect, forward_queries and the backward read the
+        same storage).  `forward_queries`' backward then gives them ordinary autograd gradients (csrc/open_vocab_bwd.hip, owl_class_logits_bwd_head).
+        They are still NOT registered parameters: parameters(), named_parameters(), state_dict(), flat_param / flat_grad / flat_offsets, FusedAdamW, its
+        EMA and ddp.DataParallel see nothing new, and no `trainable=` substring reaches them.  The caller steps them with a torch optimizer over
+        `model.logit_head_parameters()` -- the contract of a learnable `query_embeds` -- and writes them back to HF through `model.logit_head_state()`."""
         if head is None:
             self.logit_head = None
+            self._logit_head_flat = None
             return self
         D, out = self.cfg.hidden, {}
         for k in W.LOGIT_HEAD_KEYS:
@@ -954,8 +963,37 @@ class OwlViT(nn.Module):
             if t.numel() != want:
                 raise ValueError(f"set_logit_head: `{k}` must have {want} element(s) for hidden size {D}, got {t.numel()}")
             out[k] = t.contiguous().to(self.device_)
+        if trainable:
+            flat = torch.cat([out["logit_shift.weight"], out["logit_scale.weight"], out["logit_shift.bias"], out["logit_scale.bias"]])
+            at = {"logit_shift.weight": (0, D), "logit_scale.weight": (D, 2 * D), "logit_shift.bias": (2 * D, 2 * D + 1), "logit_scale.bias": (2 * D + 1, 2 * D + 2)}
+            out = {k: flat[at[k][0]:at[k][1]].detach().requires_grad_(True) for k in W.LOGIT_HEAD_KEYS}          # leaves that share the buffer's storage
+            self._logit_head_flat = flat
+        else:
+            self._logit_head_flat = None
         self.logit_head = out
         return self
+
+    def logit_head_parameters(self):
+        """The four leaf tensors of a trainable logit head (set_logit_head(head, trainable=True)), in weights.LOGIT_HEAD_KEYS' order, for a torch
+        optimizer of the caller's.  A frozen head, or none, gives an EMPTY list: torch.optim refuses it ("optimizer got an empty parameter list"), and
+        `params + model.logit_head_parameters()` adds nothing."""
+        lh = getattr(self, "logit_head", None)
+        if lh is None:
+            return []
+        return [lh[k] for k in W.LOGIT_HEAD_KEYS if lh[k].requires_grad]
+
+    def logit_head_state(self):
+        """The logit head as weights.hf_logit_head gives it -- float32 numpy, HF's shapes ([D] weights, 0-d biases) -- trained or not: prefix the keys
+        with `class_head.` (HF's weights are [1, D], biases [1]) to put a trained head back into an `OwlViTForObjectDetection` state dict;
+        `set_logit_head(model.logit_head_state())` restores the same bits.  A host copy (it synchronises)."""
+        lh = getattr(self, "logit_head", None)
+        if lh is None:
+            raise RuntimeError("logit_head_state: no logit head -- call model.set_logit_head(weights.hf_logit_head(hf_state_dict)) or load_model(..., logit_head=)")
+        out = OrderedDict()
+        for k in W.LOGIT_HEAD_KEYS:
+            v = lh[k].detach().cpu().numpy().astype(np.float32)
+            out[k] = np.ascontiguousarray(v.reshape(-1)) if k.endswith("weight") else v.reshape(()).copy()
+        return out
 
     @torch.no_grad()
     def detect(self, pixel_values, query_embeds, query_mask=None, return_scores=False):
@@ -1030,7 +1068,8 @@ class OwlViT(nn.Module):
         With grad enabled the forward runs on the TRAINING workspace, pred_boxes carry the bits of `model(image)[0]`, and backward() accumulates into
         the model's trainable set -- any set `trainable=` accepts -- exactly as the bank path does (flat_grad, FusedAdamW, the deferred tail), through
         csrc/open_vocab_bwd.hip instead of the bank head's adjoint.  What is NOT trained: the learnable bank `queries` (it takes no part and gets no
-        gradient), the four logit-head tensors (frozen buffers; the gradient passes through them to the features) and any text tower.  If
+        gradient), the four logit-head tensors unless set_logit_head(head, trainable=True) made them leaves (frozen buffers by default; the gradient
+        passes through them to the features either way; trained, their gradients arrive as ordinary autograd gradients) and any text tower.  If
         `query_embeds.requires_grad` it receives its gradient as an ordinary autograd gradient (prompt tuning: the tensor is the caller's, stepped by
         any torch optimizer; under the deferred tail the caller's stream is ordered behind it).  As with `forward`, call backward() before the next
         recording forward at the same batch size (RuntimeError otherwise).  The loss over [B, P, Q] logits is
@@ -1041,7 +1080,8 @@ class OwlViT(nn.Module):
             raise RuntimeError("forward_queries: no logit head -- call model.set_logit_head(weights.hf_logit_head(hf_state_dict)) or load_model(..., logit_head=)")
         B, Q, shared = check_detect_args(self.cfg, pixel_values, query_embeds, query_mask)
         qe = torch.as_tensor(query_embeds)
-        need_grad = torch.is_grad_enabled() and (qe.requires_grad or any(p.requires_grad for p in self.parameters()))
+        head = [self.logit_head[k] for k in W.LOGIT_HEAD_KEYS if self.logit_head[k].requires_grad] if self.logit_head else []          # a trainable head's leaves
+        need_grad = torch.is_grad_enabled() and (qe.requires_grad or bool(head) or any(p.requires_grad for p in self.parameters()))
         if not need_grad:
             return self.detect(pixel_values, qe.detach(), query_mask)
         self._check_trainable_set()
@@ -1050,7 +1090,9 @@ class OwlViT(nn.Module):
         if query_mask is not None:
             qm = (torch.as_tensor(query_mask).to(self.device_) != 0).to(torch.uint8).contiguous()
         from .autograd import OwlViTQueryFunction
-        return OwlViTQueryFunction.apply(self, pixel_values, qe, qm, *[self._byname[n] for n in self.flat_offsets])
+        if head and len(head) != 4:
+            raise RuntimeError("forward_queries: the four logit-head tensors train together or not at all (set_logit_head(head, trainable=True))")
+        return OwlViTQueryFunction.apply(self, pixel_values, qe, qm, *[self._byname[n] for n in self.flat_offsets], *head)
 
     def forward_text(self, pixel_values, input_ids, text_tower, shared=None):
         """`forward_queries` on tokenised prompts, input_ids laid out as for `detect_text`.  The text tower stays forward-only: its embeddings are
@@ -1150,7 +1192,8 @@ def check_exemplars(class_ids, query_boxes, n_images, n_classes):
 
 
 def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed: int = 1234, state=None, *,
-               prompt_ids=None, text_state=None, vocab=None, merges=None, trainable=None, image_size=None, exemplars=None, logit_head=None):
+               prompt_ids=None, text_state=None, vocab=None, merges=None, trainable=None, image_size=None, exemplars=None, logit_head=None,
+               logit_head_trainable=False):
     """ref src/models.py:149-191.  The reference downloads `google/owlvit-base-patch32` and runs the
     CLIP text tower once to initialise the query bank; neither box has network access, so weights
     come from `state` (name -> array, reference parameter names) or, by default, the deterministic
@@ -1180,7 +1223,9 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
     `vocab=` is given too (OwlViT.set_queries_from_exemplars): classes with exemplars take the image prior, the others keep the text (or random) one.
 
     `logit_head` (None = none is set): weights.hf_logit_head(sd), HF's `class_head.logit_shift / logit_scale` -- what zero-shot inference
-    (OwlViT.detect / detect_text) needs beside the vision path.  Frozen buffers outside the parameters: see OwlViT.set_logit_head."""
+    (OwlViT.detect / detect_text) needs beside the vision path.  Frozen buffers outside the parameters: see OwlViT.set_logit_head.
+    `logit_head_trainable=True` makes them four leaf tensors that `forward_queries`' backward gives gradients (still outside the parameters; stepped
+    by the caller's torch optimizer over `model.logit_head_parameters()`)."""
     n_classes = len(labelmap)
     cfg = get_config(arch, n_classes=n_classes)
     g0 = table_grid(np.asarray(state[_POS]).shape[0]) if (state is not None and _POS in state) else cfg.grid
@@ -1217,5 +1262,5 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
             raise ValueError("load_model: exemplars= is (pixel_values, class_ids) or (pixel_values, class_ids, query_boxes)")
         model.set_queries_from_exemplars(*exemplars)
     if logit_head is not None:
-        model.set_logit_head(logit_head)
+        model.set_logit_head(logit_head, trainable=logit_head_trainable)
     return model

@@ -231,13 +231,26 @@ def class_logits_bwd_workspace_bytes(B, P, Q, nbanks, Dt, want_dq=True):
     return int(nbytes.item())
 
 
-def class_logits_bwd(dlogits, e, queries, w_shift, w_scale, rowstats, B, P, mask=None, de=None, dfeats=True, dqueries=True, workspace=None):
+def class_logits_bwd_head_workspace_bytes(B, P, Q, nbanks, Dt, D, want_dq=True):
+    """Bytes of class_logits_bwd's workspace where the head's own gradients are formed (dhead; include/owl_hip.h owl_class_logits_bwd_head_workspace_bytes)."""
+    nbytes = torch.zeros(1, dtype=torch.int64)
+    _lib.call("owl_class_logits_bwd_head_workspace_bytes", int(B), int(P), int(Q), int(nbanks), int(Dt), int(D), 1 if want_dq else 0, nbytes)
+    return int(nbytes.item())
+
+
+def class_logits_bwd(dlogits, e, queries, w_shift, w_scale, rowstats, B, P, mask=None, de=None, dfeats=True, dqueries=True, workspace=None, feats=None,
+                     dhead=False, rowgrad=None):
     """The adjoint of class_logits (include/owl_hip.h owl_class_logits_bwd) on the forward's operands; rowstats is what that forward left.
     dlogits f32 [B, P, Q] (masked entries are selected to 0: anything may stand there); e f32 [>= B P, Dt]; queries f32 [B, Q, Dt] or [Q, Dt];
     w_shift / w_scale f32 [D]; rowstats f32 [>= B P, 2]; mask uint8 [B, Q] or [Q] or None.
     de: bf16 [>= B P, Dt], allocated when None.  dfeats / dqueries: True (allocate: f32 [B P, D] / f32 of queries' shape), False (not formed: the work
     is skipped) or the tensor to store into (dfeats f32 [>= B P, D]).  workspace: a uint8 device tensor of at least
-    class_logits_bwd_workspace_bytes(...) bytes, allocated when None.  -> (de, dfeats or None, dqueries or None).  No host sync."""
+    class_logits_bwd_workspace_bytes(...) bytes, allocated when None.  -> (de, dfeats or None, dqueries or None).  No host sync.
+
+    dhead: False (today's entry, unchanged), True (allocate) or an f32 [2 D + 2] tensor laid out w_shift | w_scale | b_shift | b_scale: the gradients of
+    the head's own four tensors (include/owl_hip.h owl_class_logits_bwd_head).  It needs feats, the bf16 [>= B P, D] features the forward read;
+    rowgrad is the f32 [>= B P, 2] scratch that receives (dshift, ds) per row (allocated when None) and the workspace is
+    class_logits_bwd_head_workspace_bytes(...) bytes.  -> (de, dfeats or None, dqueries or None, dhead) then."""
     _chk(dlogits, torch.float32, "dlogits"); _chk(e, torch.float32, "e"); _chk(queries, torch.float32, "queries")
     _chk(w_shift, torch.float32, "w_shift"); _chk(w_scale, torch.float32, "w_scale"); _chk(rowstats, torch.float32, "rowstats"); _chk(mask, torch.uint8, "mask")
     B, P = int(B), int(P)
@@ -281,13 +294,40 @@ def class_logits_bwd(dlogits, e, queries, w_shift, w_scale, rowstats, B, P, mask
         if tuple(dqueries.shape) != tuple(queries.shape):
             raise ValueError(f"class_logits_bwd: dqueries must be f32 {tuple(queries.shape)}, got {tuple(dqueries.shape)}")
     nbanks = B if queries.dim() == 3 else 1
-    need = class_logits_bwd_workspace_bytes(B, P, Q, nbanks, Dt, dqueries is not None)
+    if dhead is False:
+        if rowgrad is not None:
+            raise ValueError("class_logits_bwd: rowgrad is the scratch of dhead (dhead=False forms no head gradients)")
+        need, query = class_logits_bwd_workspace_bytes(B, P, Q, nbanks, Dt, dqueries is not None), "class_logits_bwd_workspace_bytes"
+    else:
+        if feats is None:
+            raise ValueError("class_logits_bwd: dhead needs feats, the bf16 [>= B P, D] features the forward read")
+        _chk(feats, torch.bfloat16, "feats")
+        if feats.dim() != 2 or feats.shape[1] != D or feats.shape[0] < B * P:
+            raise ValueError(f"class_logits_bwd: feats must be bf16 [>= {B * P}, {D}], got {tuple(feats.shape)}")
+        if dhead is True:
+            dhead = torch.empty(2 * D + 2, dtype=torch.float32, device=dev)
+        else:
+            _chk(dhead, torch.float32, "dhead")
+            if tuple(dhead.shape) != (2 * D + 2,):
+                raise ValueError(f"class_logits_bwd: dhead must be f32 [{2 * D + 2}] (w_shift | w_scale | b_shift | b_scale), got {tuple(dhead.shape)}")
+        if rowgrad is None:
+            rowgrad = torch.empty(B * P, 2, dtype=torch.float32, device=dev)
+        else:
+            _chk(rowgrad, torch.float32, "rowgrad")
+            if rowgrad.numel() < 2 * B * P:
+                raise ValueError(f"class_logits_bwd: rowgrad must hold [{B * P}, 2] floats")
+        need, query = class_logits_bwd_head_workspace_bytes(B, P, Q, nbanks, Dt, D, dqueries is not None), "class_logits_bwd_head_workspace_bytes"
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=dev)
     else:
         _chk(workspace, torch.uint8, "workspace")
         if workspace.numel() < need:
-            raise ValueError(f"class_logits_bwd: workspace must hold {need} bytes (class_logits_bwd_workspace_bytes), got {workspace.numel()}")
+            raise ValueError(f"class_logits_bwd: workspace must hold {need} bytes ({query}), got {workspace.numel()}")
+    nmasks = (B if mask.dim() == 2 else 1) if mask is not None else 1
+    if dhead is not False:
+        _lib.call("owl_class_logits_bwd_head", stream(), dlogits, e, queries, feats, w_shift, w_scale, rowstats, mask, workspace, need, rowgrad, de, dfeats,
+                  dqueries, dhead[:D], dhead[D:2 * D], dhead[2 * D:2 * D + 1], dhead[2 * D + 1:], B, P, Q, nbanks, nmasks, Dt, D)
+        return de, dfeats, dqueries, dhead
     _lib.call("owl_class_logits_bwd", stream(), dlogits, e, queries, w_shift, w_scale, rowstats, mask, workspace, need, de, dfeats, dqueries,
               B, P, Q, nbanks, (B if mask.dim() == 2 else 1) if mask is not None else 1, Dt, D)
     return de, dfeats, dqueries
