@@ -1,7 +1,10 @@
 """COCO bbox mAP on the device (csrc/metrics.hip through metrics.MeanAveragePrecision) against the numpy restatement of the protocol
 (tests/coco_eval_restatement.py).  The records (matched / ignored bits, ranks, ground-truth counts) are integers and the precision / recall arrays
 are IEEE f64 quotients of the same integers with the same eps: all compared with array_equal.  The mean summaries are compared at 1e-9 (rounding
-bound of an f64 mean over fewer than 10^6 values in [0, 1]; the device sums in another order than numpy)."""
+bound of an f64 mean over fewer than 10^6 values in [0, 1]; the device sums in another order than numpy).
+
+The edge cases aimed at the kernels' own forms (compactions, rank cut, ground-truth order, area edges, the matching chain, padding, in-kernel scaling,
+and owl_map_accumulate on hand-built records) are in tests/test_metrics_edges_gpu.py; profiles/eval_map_edges.md lists them."""
 import numpy as np
 import pytest
 import torch
