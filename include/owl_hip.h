@@ -34,7 +34,7 @@ extern "C" {
 
 /* ---- runtime ---------------------------------------------------------------------------------- */
 /* Bumped whenever a prototype, an argument's meaning or a caller-provided scratch layout changes (1 = round 1; 2 = round 2: per-call `tile` /
- * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's); still 8, additive again: + owl_gemm_nt_plan and the OWL_GEMM_KERNEL_* ids (which kernels a GEMM call launches; host query); still 8, additive again: + owl_prefix_emit, owl_prefix_gather (the frozen-prefix activation cache); still 8, additive again: + owl_image_query_workspace_bytes, owl_image_query_select, owl_query_bank_fill (the query bank from image exemplars); still 8, additive again: + owl_focal_match_cost, owl_focal_loss_workspace_bytes, owl_focal_loss_fwd, owl_box_pair_loss, owl_open_vocab_loss_reduce, owl_focal_loss_bwd, owl_box_pair_loss_bwd (the open-vocabulary criterion over [B, P, Q] logits).  owl_abi_version() returns the value
+ * `variant` arguments, partial-sum scratch of the row reductions, 5D+4 box_final_bwd partials; 3 = round 3; 4 = round 4: `slow_tiles` statistic of the attention forward; 5 = round 5: owl_patch_embed_bf16's weight layout for patch sizes that are not 2^n (gathered, no im2row); the V^T attention form, attention variants 3-5, GEMM epilogues 5 / 6 and tiles 8 / 9 / 5 / 4 moved to OWL_TUNING builds); 6 = round 6: + owl_patch_embed_scratch_bytes, owl_normalize_u8, owl_allreduce_sum_f32, `phases` of owl_attention_bwd_bf16; GEMM epilogue 1 saves quick_gelu'(u) and epilogue 8 multiplies by it; patch sizes must be even; 7: + owl_map_match, owl_map_accumulate (COCO bbox mAP of the eval loop); 8: + the wide class head for label sets beyond 10 classes (owl_query_normalize_wide, owl_class_sims_wide_fwd, owl_class_sims_wide_bwd, owl_query_normalize_wide_bwd); still 8: + owl_grad_norm_workspace_bytes, owl_grad_sumsq, owl_adamw_step_grouped (clipped AdamW with parameter groups) -- purely additive: no existing prototype, layout or meaning changes, so the number stays; still 8, additive again: + owl_embed_bwd, owl_im2row_bf16, owl_slab_reduce_rows (the backward below encoder layer 0, for trainable embeddings); still 8, additive again: + owl_bicubic_coeffs_box, owl_preprocess_u8_tiles (train-time crop / flip / mosaic in the device resampler); still 8, additive again: + owl_pos_resample, owl_pos_resample_bwd (the position table at another input size than the checkpoint's); still 8, additive again: + owl_gemm_nt_plan and the OWL_GEMM_KERNEL_* ids (which kernels a GEMM call launches; host query); still 8, additive again: + owl_prefix_emit, owl_prefix_gather (the frozen-prefix activation cache); still 8, additive again: + owl_image_query_workspace_bytes, owl_image_query_select, owl_query_bank_fill (the query bank from image exemplars); still 8, additive again: + owl_focal_match_cost, owl_focal_loss_workspace_bytes, owl_focal_loss_fwd, owl_box_pair_loss, owl_open_vocab_loss_reduce, owl_focal_loss_bwd, owl_box_pair_loss_bwd (the open-vocabulary criterion over [B, P, Q] logits); still 8, additive again: + owl_box_rows_compact_blocks, owl_box_rows_compact, owl_box_rows_gather, owl_box_rows_put, owl_box_rows_scatter_add (the box head's dX GEMMs on the rows that carry a gradient).  owl_abi_version() returns the value
  * the library was BUILT with: a binding compares it with the header it was generated from and refuses a mismatch (_lib.load() does). */
 #define OWL_ABI_VERSION 8
 const char* owl_last_error(void);
@@ -305,6 +305,21 @@ int owl_query_normalize_wide_bwd(void* stream, const float* dqhat_wide, const fl
  * du1_colsum (optional, [D]): += column sums of du1 = dense1's bias gradient, from the same pass */
 int owl_box_final_bwd_blocks(int64_t rows);
 int owl_box_final_bwd(void* stream, const float* dboxes, const float* sig, const void* h1_bf16, const void* u1_bf16, const float* w2, void* du1_bf16, float* partials, float* dw2_db2, int64_t rows, int64_t D, float* du1_colsum);
+/* The box head's two dX GEMMs on the rows that carry a gradient (csrc/box_rows_bwd.hip; still ABI 8: additive).  The box losses read pred_boxes at the
+ * matched predictions only (ref src/losses.py `src_boxes = outputs["pred_boxes"][idx]`), so dboxes f32 [rows, 4] is zero in all but at most `cap` rows, a
+ * bound the host knows without a sync.  Every kernel takes the row count from device memory; the grids are sized from cap / cap_pad (a multiple of 8, >= cap).
+ *   owl_box_rows_compact: row_list int32 [cap] = the indices of the rows with a component that is not == 0, ascending (NaN and inf count as non-zero,
+ *     -0.0 as zero; a prefix scan, no atomics); count_flag int32 [2 + owl_box_rows_compact_blocks(rows)] = {rows listed (<= cap), 1 if MORE than cap
+ *     rows were non-zero, then the compaction's own scratch}; the other kernels read its first two words.
+ *   owl_box_rows_gather: dst_k bf16 [cap_pad, D] = rows row_list[i] of src_k bf16 [rows, D], zero rows at i >= count; k = 0..2 in one launch, a NULL pair is
+ *     skipped.  A set overflow flag makes every listed row NaN instead: loud in everything computed from the compact operands.
+ *   owl_box_rows_put: dst_k bf16 [rows, D] row row_list[i] = row i of src_k bf16 [cap, D] for i < count, or zeros where src_k is NULL; k = 0, 1 in one launch.
+ *   owl_box_rows_scatter_add: dfeats f32 [rows, D] row row_list[i] += dfc f32 [cap, D] row i for i < count (distinct rows: no atomics). */
+int owl_box_rows_compact_blocks(int64_t rows);
+int owl_box_rows_compact(void* stream, const float* dboxes, int64_t rows, int64_t cap, int* row_list, int* count_flag);
+int owl_box_rows_put(void* stream, const void* src0, const void* src1, void* dst0, void* dst1, const int* row_list, const int* count_flag, int64_t rows, int64_t cap, int64_t D);
+int owl_box_rows_gather(void* stream, const void* src0, const void* src1, const void* src2, void* dst0, void* dst1, void* dst2, const int* row_list, const int* count_flag, int64_t rows, int64_t cap_pad, int64_t D);
+int owl_box_rows_scatter_add(void* stream, const float* dfc, float* dfeats, const int* row_list, const int* count_flag, int64_t rows, int64_t cap, int64_t D);
 int owl_transpose_colsum_bf16(void* stream, const void* in, int64_t ld_in, void* out_t, int64_t ld_out, float* colsum, int64_t R, int64_t C, float* partials, int64_t partials_floats);
 int owl_colsum_f32(void* stream, const float* in, float* colsum, int64_t R, int64_t C, float* partials, int64_t partials_floats);
 /* Backward below encoder layer 0 (HF5:282-288, 336-343), run only when backbone.embeddings is trainable (still ABI 8: additive).

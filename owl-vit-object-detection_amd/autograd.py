@@ -156,9 +156,9 @@ def _bws(model, B):
     Qg = _routed_cols(model)                                 # columns of the routed upstream G = rows of dqhat: 32, or the wide head's Qp
     sz = _dw_sizes(cfg, Qg, model._train_emb)
     ws = dict(
-        de=z(Mh, Dt, bf, dev), dqhat=torch.zeros(Qg, Dt, device=dev), du1=z(Mh, D, bf, dev), du0=z(Mh, D, bf, dev),
+        de=z(Mh, Dt, bf, dev), dqhat=torch.zeros(Qg, Dt, device=dev),
+        # (du1 / du0 / box_part, the [Mh, D] workspaces of a DENSE box-head backward, are made when one first runs: _box_dense_ws; the row path's: _box_rows_ws)
         g32=z(Mh, Qg, bf, dev), e_bf=z(Mh, Dt, bf, dev),
-        box_part=torch.zeros(_lib.load().owl_box_final_bwd_blocks(Mh), 5 * D + 4, device=dev),
         slab=torch.zeros(sz.slab, device=dev),
         sink=torch.zeros(4 * D + 8, device=dev),          # where kernels that must run leave the gradients of FROZEN tensors (never read; not in the bucket)
         # per-split partial sums of the bias gradients (one row of n_out floats per split of the dW GEMM; at most 256 splits); the class head's chain has its own
@@ -193,6 +193,59 @@ def _bws(model, B):
     ws["dw_enc"] = dict(slab=ws["slab"], part=ws["part2"], bslab=ws["bslab"], tA=ws["tA"], tB=ws["tB"], tn_all=sz.tn_all)
     model._ws[key] = ws
     return ws
+
+
+def _box_dense_ws(model, B, bw, du0=True):
+    """du1 (and du0) bf16 [Mh, D] and the tail's partials of the box-head backward, allocated when first needed at this batch size: the row path reads du1
+    alone, so a run whose box gradients all come marked from the criterion never makes the 113 MB du0."""
+    D, Mh, dev = model.cfg.hidden, B * model.cfg.patches, model.device_
+    if "du1" not in bw:
+        bw["du1"] = ops.zeros_rows(Mh, D, torch.bfloat16, dev)
+        bw["box_part"] = torch.zeros(_lib.load().owl_box_final_bwd_blocks(Mh), 5 * D + 4, device=dev)
+    if du0 and "du0" not in bw:
+        bw["du0"] = ops.zeros_rows(Mh, D, torch.bfloat16, dev)
+    return bw
+
+
+def _box_rows_ws(model, B, bw, cap_pad):
+    """The row path's workspaces at this batch size, grown to the largest bound seen: the row list and (count, overflow flag) and the compact operands
+    [pad_rows(cap_pad), D] (rows beyond cap_pad stay zero: never written).  Where the box head trains, also du0z: a dense bf16 [Mh, D] buffer that is all
+    zero between backwards (the listed rows of du0 are put in for dense0's weight-gradient product and cleared after it)."""
+    rw = bw.get("box_rows")
+    if rw is None or rw["cap_pad"] < cap_pad:
+        D, dev = model.cfg.hidden, model.device_
+        bf, z = torch.bfloat16, ops.zeros_rows
+        rw = dict(cap_pad=cap_pad, row_list=torch.zeros(cap_pad, dtype=torch.int32, device=dev),
+                  count_flag=torch.zeros(ops.box_rows_state_ints(B * model.cfg.patches), dtype=torch.int32, device=dev),
+                  du1c=z(cap_pad, D, bf, dev), du0c=z(cap_pad, D, bf, dev), ub0c=z(cap_pad, D, bf, dev), dfc=z(cap_pad, D, torch.float32, dev),
+                  du0z=None if rw is None else rw["du0z"])
+        bw["box_rows"] = rw
+    if "box_head" in model._units and rw["du0z"] is None:
+        rw["du0z"] = ops.zeros_rows(B * model.cfg.patches, model.cfg.hidden, torch.bfloat16, model.device_)
+    return rw
+
+
+BOX_ROWS_MARK = "_owl_box_rows_cap"          # attribute the criteria put on the box gradient they return: at most that many rows of it are non-zero
+
+
+def mark_box_rows(d_boxes, cap):
+    """The promise of a criterion whose box loss reads the matched predictions only (losses._PushPullFn / _OpenVocabFn): at most `cap` rows of the
+    [B, P, 4] gradient it returns are non-zero.  backward_impl then runs the box head's dX GEMMs on those rows.  A broken promise is loud, not wrong: more
+    than `cap` non-zero rows turn dense0's gradients and d(feats) into NaN (csrc/box_rows_bwd.hip)."""
+    setattr(d_boxes, BOX_ROWS_MARK, int(cap))
+    return d_boxes
+
+
+def _box_rows_cap(model, d_boxes, B, P):
+    """The bound of a marked box gradient the row path takes, or None: the dense launches."""
+    cap = getattr(d_boxes, BOX_ROWS_MARK, None)
+    if cap is None or getattr(model, "box_backward", "auto") != "auto":
+        return None
+    if d_boxes.dtype != torch.float32 or not d_boxes.is_contiguous() or tuple(d_boxes.shape) != (B, P, 4):
+        return None
+    if ops.box_rows_cap_pad(cap) * 8 > B * P:          # (tiny configs with many targets: nothing to gain)
+        return None
+    return int(cap)
 
 
 def _split_k(n_rows_out, n_cols_out, k):
@@ -321,6 +374,9 @@ def backward_impl(model, B, d_boxes, d_sims, sims, logit_head=None):
     below_heads = floor != "heads"                # the dX chain goes on below feats
     below_enc = floor in ("pre_layernorm", "embeddings")
     LP = lambda i: f"backbone.encoder.layers.{i}."
+    if getattr(model, "box_backward", "auto") not in ("auto", "dense"):
+        raise ValueError(f"model.box_backward must be 'auto' or 'dense', got {model.box_backward!r}")
+    box_cap = _box_rows_cap(model, d_boxes, B, P)          # (read off the tensor autograd handed over: a copy below would not carry the mark)
     d_boxes = d_boxes.contiguous().float()
     if logit_head is None:
         d_sims = d_sims.contiguous().float()
@@ -402,8 +458,15 @@ def backward_impl(model, B, d_boxes, d_sims, sims, logit_head=None):
         if hs is not main0:
             ev_h[1].record(hs)
     # ---- box head -------------------------------------------------------------------------------------
-    w0T = None
+    # A box gradient that comes marked from the criterion (mark_box_rows: at most `cap` non-zero rows) runs the section's two dX GEMMs -- du0 through the
+    # erf-GELU' and the product into d(feats): 340 of the section's 660 us at B/16 batch 32 -- on those rows: compaction -> gather -> the GEMMs at M = cap_pad
+    # -> scatter-add into d(feats).  Every GEMM row depends on its own A row alone: same bits.  The sums over rows (the tail kernel, the two weight-gradient
+    # products) stay the dense launches they were, dense0's on du0z = the listed rows of du0 where they lie in a buffer that is zero elsewhere (a zero row
+    # adds exact zeros): every gradient keeps its bits, and a training run its trajectory.
+    w0T = rw = None
     if t_box or below_heads:
+        model.last_box_backward = "dense" if box_cap is None else "rows"
+        _box_dense_ws(model, B, bw, du0=box_cap is None)
         if t_box:
             gw2, gb2 = G("box_head.dense2.weight"), G("box_head.dense2.bias")
             assert gb2.data_ptr() == gw2.data_ptr() + 4 * gw2.numel(), "dense2 weight/bias grads must be adjacent in the flat bucket"
@@ -413,18 +476,35 @@ def backward_impl(model, B, d_boxes, d_sims, sims, logit_head=None):
                           du1_colsum=G("box_head.dense1.bias") if t_box else None)          # (dense1's bias gradient from the same pass: no column-sum launch over du1)
         if t_box:
             weight_grad(bw["du1"], ws["hb0"], G("box_head.dense1.weight"), D, D, Mh, bw["dw_main"])
-        ops.gemm(ops.EPI_DGELU_BF16, bw["du1"], wT("box_head.dense1.weight", D, D), bw["du0"], aux=ws["ub0"], M=Mh, N=D, K=D)
-        if t_box:
-            weight_grad(bw["du0"], ws["feats"], G("box_head.dense0.weight"), D, D, Mh, bw["dw_main"], G("box_head.dense0.bias"))
-        if below_heads:
-            w0T = wT("box_head.dense0.weight", D, D)
+        if box_cap is not None:
+            cap_pad = ops.box_rows_cap_pad(box_cap)
+            rw = _box_rows_ws(model, B, bw, cap_pad)
+            rl, cf = rw["row_list"], rw["count_flag"]
+            ops.box_rows_compact(d_boxes, Mh, box_cap, rl, cf)
+            ops.box_rows_gather([(bw["du1"], rw["du1c"]), (ws["ub0"], rw["ub0c"])], rl, cf, Mh, cap_pad, D)
+            ops.gemm(ops.EPI_DGELU_BF16, rw["du1c"], wT("box_head.dense1.weight", D, D), rw["du0c"], aux=rw["ub0c"], M=cap_pad, N=D, K=D)
+            if t_box:
+                ops.box_rows_put([(rw["du0c"], rw["du0z"])], rl, cf, Mh, box_cap, D)
+                weight_grad(rw["du0z"], ws["feats"], G("box_head.dense0.weight"), D, D, Mh, bw["dw_main"], G("box_head.dense0.bias"))
+                ops.box_rows_put([(None, rw["du0z"])], rl, cf, Mh, box_cap, D)
+            if below_heads:
+                ops.gemm(ops.EPI_F32, rw["du0c"], wT("box_head.dense0.weight", D, D), rw["dfc"], M=cap_pad, N=D, K=D)
+        else:
+            ops.gemm(ops.EPI_DGELU_BF16, bw["du1"], wT("box_head.dense1.weight", D, D), bw["du0"], aux=ws["ub0"], M=Mh, N=D, K=D)
+            if t_box:
+                weight_grad(bw["du0"], ws["feats"], G("box_head.dense0.weight"), D, D, Mh, bw["dw_main"], G("box_head.dense0.bias"))
+            if below_heads:
+                w0T = wT("box_head.dense0.weight", D, D)
     if hs is not main0:
         main0.wait_event(ev_h[1])                 # d(feats) of the class head is in place (and the side stream's scratch is free again)
     if logit_head is not None and logit_head.get("event") is not None:
         logit_head["event"].record(main0)         # the query gradient is complete on this stream from here on
     if not below_heads:
         return
-    ops.gemm(ops.EPI_ACC_F32, bw["du0"], w0T, bw["dfeats"], M=Mh, N=D, K=D)
+    if rw is not None:
+        ops.box_rows_scatter_add(rw["dfc"], bw["dfeats"], rw["row_list"], rw["count_flag"], Mh, box_cap, D)
+    else:
+        ops.gemm(ops.EPI_ACC_F32, bw["du0"], w0T, bw["dfeats"], M=Mh, N=D, K=D)
     # ---- merge + the two final LayerNorms --------------------------------------------------------------
     # (the kernel takes no null for the four affine gradients: those of a frozen LayerNorm go to the sink)
     sink = bw["sink"]

@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
+from .autograd import mark_box_rows
 from .matcher import HungarianMatcher, PackedTargets, box_iou, generalized_box_iou  # noqa: F401  (re-exported like the reference)
 from .matcher import OpenVocabMatcher, _mask_u8, pack_open_vocab_targets
 
@@ -33,6 +34,7 @@ class _PushPullFn(torch.autograd.Function):
         _lib.call("owl_push_pull_loss", s, sims, boxes, tc, crit.scales, tg.boxes, pred_idx, tgt_idx, tg.counts, per_image,
                   losses, dsims, dl1, dgiou, B, P, C, tg.Nmax, crit.background_label)
         ctx.saved = (tc, dsims, dl1, dgiou, B, P, C, crit.background_label)
+        ctx.box_rows_cap = B * tg.Nmax          # the box losses read the matched predictions only: no other row of d(pred_boxes) can be non-zero
         crit.last = dict(target_classes=tc, pred_idx=pred_idx, tgt_idx=tgt_idx, per_image=per_image, sizes=tg.sizes)
         # four scalar outputs (not one 4-vector indexed afterwards: each index would cost a zero-fill + a copy in its backward)
         return losses[0], losses[1], losses[2], losses[3]
@@ -45,7 +47,7 @@ class _PushPullFn(torch.autograd.Function):
         out_sims = torch.empty(B, P, C, device=dev)
         out_boxes = torch.empty(B, P, 4, device=dev)
         _lib.call("owl_push_pull_loss_bwd", ops.stream(), g, tc, dsims, dl1, dgiou, out_sims, out_boxes, B, P, C, bg)
-        return out_sims, out_boxes, None, None
+        return out_sims, mark_box_rows(out_boxes, ctx.box_rows_cap), None, None
 
 
 class PushPullLoss(nn.Module):
@@ -95,6 +97,7 @@ class _OpenVocabFn(torch.autograd.Function):
         _lib.call("owl_open_vocab_loss_reduce", s, ws, ws.numel() * 8, losses, B, P, Q, float(num_boxes))
         # (the logits themselves are kept, not an unscaled gradient tensor: the backward recomputes the focal term from x and t)
         ctx.saved = (lg, mask_u8, nmasks, tc, dl1, dgiou, float(crit.alpha), float(num_boxes))
+        ctx.box_rows_cap = B * tg.Nmax          # (as in _PushPullFn.forward)
         crit.last = dict(target_classes=tc, pred_idx=pred_idx, tgt_idx=tgt_idx, sizes=tg.sizes, num_boxes=float(num_boxes))
         # three scalar outputs, not one 3-vector indexed afterwards (see _PushPullFn.forward)
         return losses[0], losses[1], losses[2]
@@ -110,7 +113,7 @@ class _OpenVocabFn(torch.autograd.Function):
         s = ops.stream()
         _lib.call("owl_focal_loss_bwd", s, g, lg, mask_u8, tc, dlogits, B, P, Q, nmasks, alpha, num_boxes)
         _lib.call("owl_box_pair_loss_bwd", s, g, dl1, dgiou, dboxes, B, P, num_boxes)
-        return dlogits, dboxes, None, None, None, None, None
+        return dlogits, mark_box_rows(dboxes, ctx.box_rows_cap), None, None, None, None, None
 
 
 class OpenVocabLoss(nn.Module):

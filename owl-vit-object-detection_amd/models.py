@@ -231,6 +231,12 @@ class OwlViT(nn.Module):
         # faster (three alternated rounds: +0.17 / -0.38 / -0.23 %): the in-backward form stays the default.
         self.pretranspose = False
         self._wt, self._wt_stream_, self._wt_event = None, None, None
+        # box_backward: "auto" = a box gradient that comes marked from the criterion (autograd.mark_box_rows: PushPullLoss / OpenVocabLoss read the matched
+        # predictions only, so all but at most B * Nmax rows of it are zero) runs the box head's two dX GEMMs on those rows (csrc/box_rows_bwd.hip; the
+        # sums over rows stay dense launches: every gradient bitwise the dense section's); any other gradient takes the dense launches.
+        # "dense" = always the dense launches (A/B).  last_box_backward: "rows" | "dense", the path the last backward's box-head section took (None: none ran).
+        self.box_backward = "auto"
+        self.last_box_backward = None
         self._trainable = frozenset(order)
         # checkpointing while a deferred optimizer step (ddp.DataParallel(overlap=True)) is still running on its side stream: order the
         # current stream behind it before any parameter is read

@@ -447,6 +447,65 @@ def box_final_bwd(dboxes, sig, h1, u1, w2, du1, partials, dw2_db2, rows, D, du1_
     _lib.call("owl_box_final_bwd", stream(), dboxes, sig, h1, u1, w2, du1, partials, dw2_db2, rows, D, du1_colsum)
 
 
+# ---- the box head's dX GEMMs on the rows that carry a gradient (csrc/box_rows_bwd.hip) ----
+def box_rows_cap_pad(cap: int) -> int:
+    """Rows of the compact operands for a bound of `cap` non-zero rows: the next multiple of 8."""
+    return (max(int(cap), 1) + 7) // 8 * 8
+
+
+def box_rows_state_ints(rows: int) -> int:
+    """int32 elements of the compaction's `count_flag`: (count, overflow flag) + one count per workgroup of owl_box_rows_compact."""
+    return 2 + _lib.load().owl_box_rows_compact_blocks(int(rows))
+
+
+def box_rows_compact(dboxes, rows, cap, row_list, count_flag):
+    """row_list int32 [>= cap] = ascending indices of the rows of dboxes f32 [rows, 4] with a component that is not == 0; count_flag int32
+    [box_rows_state_ints(rows)] = (rows listed, 1 if more than cap were non-zero, then the compaction's scratch).  No host sync."""
+    _chk(dboxes, torch.float32, "dboxes"); _chk(row_list, torch.int32, "row_list"); _chk(count_flag, torch.int32, "count_flag")
+    rows, cap = int(rows), int(cap)
+    if dboxes.numel() < 4 * rows or row_list.numel() < cap or count_flag.numel() < box_rows_state_ints(rows):
+        raise ValueError("box_rows_compact: dboxes [rows, 4], row_list [>= cap], count_flag [box_rows_state_ints(rows)]")
+    _lib.call("owl_box_rows_compact", stream(), dboxes, rows, cap, row_list, count_flag)
+
+
+def box_rows_put(pairs, row_list, count_flag, rows, cap, D):
+    """pairs: one or two (src bf16 [>= cap, D] or None, dst bf16 [>= rows, D]): dst[row_list[i]] = src[i] for i < count -- zeros where src is None."""
+    rows, cap, D = int(rows), int(cap), int(D)
+    if not 1 <= len(pairs) <= 2:
+        raise ValueError("box_rows_put: one or two (source, destination) pairs")
+    for src, dst in pairs:
+        _chk(src, torch.bfloat16, "src"); _chk(dst, torch.bfloat16, "dst")
+        if dst is None or dst.numel() < rows * D or dst.shape[-1] != D or (src is not None and (src.numel() < cap * D or src.shape[-1] != D)):
+            raise ValueError("box_rows_put: src [>= cap, D] or None, dst [>= rows, D]")
+    _chk(row_list, torch.int32, "row_list"); _chk(count_flag, torch.int32, "count_flag")
+    pairs = list(pairs) + [(None, None)] * (2 - len(pairs))
+    _lib.call("owl_box_rows_put", stream(), pairs[0][0], pairs[1][0], pairs[0][1], pairs[1][1], row_list, count_flag, rows, cap, D)
+
+
+def box_rows_gather(pairs, row_list, count_flag, rows, cap_pad, D):
+    """pairs: up to three (src bf16 [>= rows, D], dst bf16 [>= cap_pad, D]): dst[i] = src[row_list[i]] for i < count, zero rows up to cap_pad.  One launch."""
+    pairs = [p for p in pairs if p is not None]
+    rows, cap_pad, D = int(rows), int(cap_pad), int(D)
+    if not 1 <= len(pairs) <= 3:
+        raise ValueError("box_rows_gather: one to three (source, destination) pairs")
+    for src, dst in pairs:
+        _chk(src, torch.bfloat16, "src"); _chk(dst, torch.bfloat16, "dst")
+        if src.numel() < rows * D or dst.numel() < cap_pad * D or src.shape[-1] != D or dst.shape[-1] != D:
+            raise ValueError("box_rows_gather: src [>= rows, D], dst [>= cap_pad, D]")
+    _chk(row_list, torch.int32, "row_list"); _chk(count_flag, torch.int32, "count_flag")
+    pairs = pairs + [(None, None)] * (3 - len(pairs))
+    _lib.call("owl_box_rows_gather", stream(), pairs[0][0], pairs[1][0], pairs[2][0], pairs[0][1], pairs[1][1], pairs[2][1], row_list, count_flag, rows, cap_pad, D)
+
+
+def box_rows_scatter_add(dfc, dfeats, row_list, count_flag, rows, cap, D):
+    """dfeats f32 [>= rows, D] row row_list[i] += dfc f32 [>= cap, D] row i for i < count."""
+    _chk(dfc, torch.float32, "dfc"); _chk(dfeats, torch.float32, "dfeats"); _chk(row_list, torch.int32, "row_list"); _chk(count_flag, torch.int32, "count_flag")
+    rows, cap, D = int(rows), int(cap), int(D)
+    if dfc.numel() < cap * D or dfeats.numel() < rows * D:
+        raise ValueError("box_rows_scatter_add: dfc [>= cap, D], dfeats [>= rows, D]")
+    _lib.call("owl_box_rows_scatter_add", stream(), dfc, dfeats, row_list, count_flag, rows, cap, D)
+
+
 def transpose_colsum(src, dst, colsum, R, C, ld_in=None, ld_out=None, partials=None):
     part = _part(partials, R, C, src.device) if colsum is not None else None
     _lib.call("owl_transpose_colsum_bf16", stream(), src, ld_in if ld_in is not None else src.shape[-1], dst,
