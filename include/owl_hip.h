@@ -85,6 +85,12 @@ int owl_slab_reduce(void* stream, const float* slabs, float* out, int64_t n, int
  * tile: 0 = automatic (two-phase ping-pong kernel for big problems), 7 / 256 / 128 pin a kernel (tests); same bits.       */
 int owl_patch_embed_scratch_bytes(int64_t B, int64_t S, int64_t ps, int64_t D, int tile, int64_t* bytes);
 int owl_patch_embed_bf16(void* stream, const void* image_bf16, const void* w_pe, const float* pos, float* x_out, void* scratch, int64_t B, int64_t S, int64_t ps, int64_t D, int64_t Tp, int tile);
+/* Rectangular images (still ABI 8: additive).  image bf16 [B, 3, H, W]; gh = H / ps, gw = W / ps; patch p = y * gw + x (the order of conv2d(...).flatten(2))
+ * goes to row b * Tp + 1 + p.  The same kernels as the square entries, which ARE these with H = W = S (same bits): the gather's row stride and patch-row
+ * divisor are W and gw, its channel stride H * W.  Refused before any launch: H or W no multiple of ps; ps odd or outside 8 .. 64 (W is then even, which the
+ * 16-byte LDS-DMA pieces need); Tp < gh * gw + 1; B * 3 * H * W * 2 >= 2^32 or B * gh * gw >= 2^31 (32-bit gather offsets).                                */
+int owl_patch_embed_scratch_bytes_hw(int64_t B, int64_t H, int64_t W, int64_t ps, int64_t D, int tile, int64_t* bytes);
+int owl_patch_embed_bf16_hw(void* stream, const void* image_bf16, const void* w_pe, const float* pos, float* x_out, void* scratch, int64_t B, int64_t H, int64_t W, int64_t ps, int64_t D, int64_t Tp, int tile);
 /* class-token rows x[b*Tp, :] = class_embedding + pos[0, :]  (HF5:338-343)                        */
 int owl_cls_rows(void* stream, float* x, const float* cls, const float* pos, int64_t B, int64_t Tp, int64_t D);
 /* Position table at another input size than the checkpoint's (HF5:296-332 `interpolate_pos_encoding`; still ABI 8: additive).  pos f32 [g0 g0 + 1, D] is
@@ -99,6 +105,11 @@ int owl_cls_rows(void* stream, float* x, const float* cls, const float* pos, int
  * 1 <= g0, g <= 256 (g0 < 4: every tap clamped); D % 8 == 0; rows 16-byte aligned.  One launch each, no scratch.                                        */
 int owl_pos_resample(void* stream, const float* pos, float* out, int64_t g0, int64_t g, int64_t D);
 int owl_pos_resample_bwd(void* stream, const float* dU, float* dpos, int64_t g0, int64_t g, int64_t D);
+/* The same pair onto a rectangular run grid (still ABI 8: additive): the native table stays [g0 g0 + 1, D], the run table is [gh gw + 1, D] with row
+ * 1 + y gw + x; the y axis takes its taps with gh, the x axis with gw (HF's interpolate(size=(gh, gw))).  Same kernels, evaluation order and fmaf count; the
+ * square entries are these with gh = gw = g.  1 <= g0, gh, gw <= 256.                                                                                       */
+int owl_pos_resample_hw(void* stream, const float* pos, float* out, int64_t g0, int64_t gh, int64_t gw, int64_t D);
+int owl_pos_resample_bwd_hw(void* stream, const float* dU, float* dpos, int64_t g0, int64_t gh, int64_t gw, int64_t D);
 
 /* ---- LayerNorm (HF5:484-486, 721-723; eps 1e-5).  out bf16 or f32 (may alias x); stats = (mean,rstd) */
 int owl_layernorm_fwd(void* stream, const float* x, const float* gamma, const float* beta, void* out, int out_bf16, float* stats, int64_t rows, int64_t D, float eps);
@@ -331,6 +342,8 @@ int owl_colsum_f32(void* stream, const float* in, float* colsum, int64_t R, int6
  * columns [3 ps^2, ld_out) are not written.  ps even.                                                                                                    */
 int owl_embed_bwd(void* stream, const float* dx, float* dpos, float* dcls, void* dE_bf16, int64_t B, int64_t T, int64_t Tp, int64_t D);
 int owl_im2row_bf16(void* stream, const void* image_bf16, void* out_bf16, int64_t ld_out, int64_t B, int64_t S, int64_t ps);
+/* owl_im2row_bf16 on a rectangular image bf16 [B, 3, H, W] -> out [B (H / ps) (W / ps), ld_out], row (b gh + gy) gw + gx (still ABI 8: additive). */
+int owl_im2row_bf16_hw(void* stream, const void* image_bf16, void* out_bf16, int64_t ld_out, int64_t B, int64_t H, int64_t W, int64_t ps);
 /* owl_slab_reduce for slabs with pad columns: out [rows, cols] (+)= sum_s slabs[s * slab_stride + r * ld_slab + c], splits added in index order.  For a split-K
  * weight gradient whose inner size is no multiple of 8 (owl_gemm_nt_bf16 needs N % 8 == 0: the 588 columns of L/14's patch embedding run as 592).  cols, ld_slab % 4 == 0 */
 int owl_slab_reduce_rows(void* stream, const float* slabs, float* out, int64_t rows, int64_t cols, int64_t ld_slab, int64_t slab_stride, int nsplit, int accumulate);

@@ -650,6 +650,6 @@ def backward_impl(model, B, d_boxes, d_sims, sims, logit_head=None):
             dU = pw["dU"]
             dU.zero_()
             ops.embed_bwd(bw["dxm"], dU, G("backbone.embeddings.class_embedding"), pw["dE"], B, T, Tp, D)
-            ops.pos_resample_bwd(dU, g_pos, cfg.native_grid, cfg.grid, D)
-        ops.im2row_bf16(ws["img"], pw["patches"], B, cfg.image_size, cfg.patch_size)
+            ops.pos_resample_bwd_hw(dU, g_pos, cfg.native_grid, cfg.grid_h, cfg.grid_w, D)
+        ops.im2row_bf16_hw(ws["img"], pw["patches"], B, *cfg.image_hw, cfg.patch_size)
         patch_weight_grad(pw["dE"], pw["patches"], G("backbone.embeddings.patch_embedding.weight").view(D, cfg.patch_k), D, cfg.patch_k, Mh, scratch=bw["dw_main"])

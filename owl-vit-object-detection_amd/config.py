@@ -11,12 +11,22 @@ from dataclasses import dataclass, asdict
 from math import isqrt
 
 MAX_PATCHES = 8192     # P ceiling of owl_spread_labels / owl_postprocess (one workgroup walks an image's patches)
+MAX_GRID_SIDE = 256    # side ceiling of either grid of owl_pos_resample_hw (only a rectangle can reach it below MAX_PATCHES)
+
+
+def image_hw(image_size):
+    """(H, W) of an `image_size` given as an int (square) or a pair (height, width)."""
+    if isinstance(image_size, (tuple, list)):
+        if len(image_size) != 2:
+            raise ValueError(f"image_size={image_size!r}: an int (square) or a pair (height, width)")
+        return int(image_size[0]), int(image_size[1])
+    return int(image_size), int(image_size)
 
 
 @dataclass(frozen=True)
 class OwlConfig:
     name: str
-    image_size: int
+    image_size: int      # S (square) or (H, W); a pair with H == W is stored as the int, so a square config has one form
     patch_size: int
     hidden: int          # D
     heads: int           # H (dh = D / H must be 64)
@@ -27,13 +37,43 @@ class OwlConfig:
     ln_eps: float = 1e-5
     pos_grid: int = 0    # side of the NATIVE position table (the checkpoint's); 0 = `grid`.  Another value: the table is resampled to `grid` (models.OwlViT)
 
+    def __post_init__(self):
+        if isinstance(self.image_size, (tuple, list)):
+            H, W = image_hw(self.image_size)
+            object.__setattr__(self, "image_size", H if H == W else (H, W))
+
+    @property
+    def image_hw(self) -> tuple:       # (H, W)
+        return image_hw(self.image_size)
+
+    @property
+    def is_square(self) -> bool:
+        return not isinstance(self.image_size, tuple)
+
+    @property
+    def grid_h(self) -> int:           # gh
+        return self.image_hw[0] // self.patch_size
+
+    @property
+    def grid_w(self) -> int:           # gw
+        return self.image_hw[1] // self.patch_size
+
     @property
     def grid(self) -> int:
+        if not self.is_square:         # a square-only consumer must not compute on the wrong grid
+            raise ValueError(f"OwlConfig.grid: image_size={self.image_size} is not square ({self.grid_h} x {self.grid_w} patches); use grid_h and grid_w")
         return self.image_size // self.patch_size
 
     @property
     def native_grid(self) -> int:      # g0
+        if not self.pos_grid and not self.is_square:
+            raise ValueError(f"OwlConfig: image_size={self.image_size} is not square, so the side of the native (square) position table cannot be "
+                             "taken from it: set pos_grid (load_model(..., image_size=(H, W)) does)")
         return self.pos_grid or self.grid
+
+    @property
+    def resampled(self) -> bool:       # the run table is a resample of the native one.  Decided by the grid, not by P: 4 x 9 has the 36 patches of 6 x 6
+        return (self.grid_h, self.grid_w) != (self.native_grid, self.native_grid)
 
     @property
     def pos_rows(self) -> int:         # rows of the position-embedding PARAMETER: g0 * g0 + 1, whatever the input size
@@ -41,7 +81,7 @@ class OwlConfig:
 
     @property
     def patches(self) -> int:          # P
-        return self.grid * self.grid
+        return self.grid_h * self.grid_w
 
     @property
     def tokens(self) -> int:           # T = P + 1 (class token first, HF5:338-339)
@@ -132,10 +172,34 @@ def table_grid(pos_rows: int) -> int:
     return g0
 
 
-def check_image_size(image_size: int, patch_size: int, pos_rows: int = None) -> int:
-    """Host-side validation of a requested (square) input size: a positive multiple of the patch size, at most MAX_PATCHES patches, and -- given the
-    row count of the position table it will be run with -- a table that is a class row plus a square grid.  -> the run grid g.  Every failure is a
-    ValueError naming the nearest valid sizes."""
+def _check_image_hw(H: int, W: int, p: int):
+    """check_image_size for a pair (height, width) -> (gh, gw)."""
+    for side, v in (("height", H), ("width", W)):
+        if v < p or v % p:
+            lo, hi = max(v // p, 1) * p, (max(v // p, 0) + 1) * p
+            near = f"{lo} and {hi}" if lo != hi and hi <= MAX_GRID_SIDE * p else f"{min(lo, MAX_GRID_SIDE * p)}"
+            raise ValueError(f"image_size=({H}, {W}): the {side} {v} is not a positive multiple of the patch size {p}; the nearest sizes that are: {near}")
+    gh, gw = H // p, W // p
+    for side, g, other in (("height", gh, gw), ("width", gw, gh)):
+        if g > MAX_GRID_SIDE:
+            raise ValueError(f"image_size=({H}, {W}): the {side} gives {g} patches of {p} pixels; the position-table kernels take grids of at most "
+                             f"{MAX_GRID_SIDE} per side: the largest {side} is {MAX_GRID_SIDE * p}")
+    if gh * gw > MAX_PATCHES:
+        raise ValueError(f"image_size=({H}, {W}) gives {gh * gw} patches of {p} pixels ({gh} x {gw}); the loss and post-process kernels take at most "
+                         f"{MAX_PATCHES} per image: the largest height at this width is {min(MAX_PATCHES // gw, MAX_GRID_SIDE) * p}, the largest width at this "
+                         f"height {min(MAX_PATCHES // gh, MAX_GRID_SIDE) * p}")
+    return gh, gw
+
+
+def check_image_size(image_size, patch_size: int, pos_rows: int = None):
+    """Host-side validation of a requested input size, an int (square) or a pair (height, width): each side a positive multiple of the patch size, at most
+    MAX_PATCHES patches (a pair: at most MAX_GRID_SIDE per side as well), and -- given the row count of the position table it will be run with -- a table
+    that is a class row plus a square grid.  -> the run grid: g for an int, (gh, gw) for a pair.  Every failure is a ValueError naming the nearest valid sizes."""
+    if isinstance(image_size, (tuple, list)):
+        grid = _check_image_hw(*image_hw(image_size), int(patch_size))
+        if pos_rows is not None:
+            table_grid(pos_rows)
+        return grid
     S, p = int(image_size), int(patch_size)
     top = isqrt(MAX_PATCHES) * p
     if S < p or S % p:

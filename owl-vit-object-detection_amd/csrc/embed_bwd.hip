@@ -47,40 +47,45 @@ OWL_API int owl_embed_bwd(void* stream, const float* dx, float* dpos, float* dcl
     return 0;
 }
 
-// im2row of the bf16 image [B, 3, S, S] in the conv weight's own column order: out[(b * G + gy) * G + gx][(c * ps + i) * ps + j] =
-// image[b][c][gy * ps + i][gx * ps + j] (G = S / ps), row stride ld >= 3 ps^2 (columns past 3 ps^2 are left alone) = the X operand of the
+// im2row of the bf16 image [B, 3, H, W] in the conv weight's own column order: out[(b * gh + gy) * gw + gx][(c * ps + i) * ps + j] =
+// image[b][c][gy * ps + i][gx * ps + j] (gh = H / ps, gw = W / ps), row stride ld >= 3 ps^2 (columns past 3 ps^2 are left alone) = the X operand of the
 // patch-embedding weight gradient.  V bf16 per lane: 8 (16 bytes) where the patch size is a multiple of 8, else 2 (a 14-pixel patch row is 4-byte aligned only).
 template <int V>
-__global__ __launch_bounds__(256) void im2row_kernel(const bf16_t* __restrict__ img, bf16_t* __restrict__ out, int64_t rows, int S, int ps, int64_t ld) {
+__global__ __launch_bounds__(256) void im2row_kernel(const bf16_t* __restrict__ img, bf16_t* __restrict__ out, int64_t rows, int H, int W, int ps, int64_t ld) {
     const int per_row = 3 * ps * (ps / V);
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= rows * per_row) return;
     const int64_t row = idx / per_row;
     const int k = (int)(idx % per_row) * V;                  // column (c * ps + i) * ps + j, j a multiple of V
     const int j = k % ps, ci = k / ps, i = ci % ps, c = ci / ps;
-    const int G = S / ps;
-    const int gx = (int)(row % G), gy = (int)((row / G) % G);
-    const int64_t b = row / ((int64_t)G * G);
-    const bf16_t* src = img + ((b * 3 + c) * S + (int64_t)gy * ps + i) * S + (int64_t)gx * ps + j;
+    const int gw = W / ps, gh = H / ps;
+    const int gx = (int)(row % gw), gy = (int)((row / gw) % gh);
+    const int64_t b = row / ((int64_t)gh * gw);
+    const bf16_t* src = img + ((b * 3 + c) * H + (int64_t)gy * ps + i) * W + (int64_t)gx * ps + j;
     bf16_t* dst = out + row * ld + k;
     if constexpr (V == 8) *(uint4*)dst = *(const uint4*)src;
     else *(unsigned*)dst = *(const unsigned*)src;
 }
 
-OWL_API int owl_im2row_bf16(void* stream, const void* image_bf16, void* out_bf16, int64_t ld_out, int64_t B, int64_t S, int64_t ps) {
+OWL_API int owl_im2row_bf16_hw(void* stream, const void* image_bf16, void* out_bf16, int64_t ld_out, int64_t B, int64_t H, int64_t W, int64_t ps) {
     OWL_CHECK_ARG(image_bf16 && out_bf16, "owl_im2row_bf16: null pointer");
-    OWL_CHECK_ARG(B >= 1 && ps >= 2 && ps % 2 == 0 && ps <= 64 && S >= ps && S % ps == 0 && S <= 8192 && B < (1 << 20), "owl_im2row_bf16: even patch size 2 .. 64 that divides the image size");
+    OWL_CHECK_ARG(B >= 1 && ps >= 2 && ps % 2 == 0 && ps <= 64 && H >= ps && H % ps == 0 && H <= 8192 && W >= ps && W % ps == 0 && W <= 8192 && B < (1 << 20),
+                  "owl_im2row_bf16: even patch size 2 .. 64 that divides the image size");
     OWL_CHECK_ARG(ld_out >= 3 * ps * ps && ld_out % 8 == 0, "owl_im2row_bf16: ld_out >= 3 ps^2 and a multiple of 8");
-    const int64_t rows = B * (S / ps) * (S / ps);
-    if (ps % 8 == 0 && S % 8 == 0) {
+    const int64_t rows = B * (H / ps) * (W / ps);
+    if (ps % 8 == 0) {          // (then W % 8 == 0 as well: every 16-byte piece is aligned)
         const int64_t n = rows * 3 * ps * (ps / 8);
-        hipLaunchKernelGGL(im2row_kernel<8>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)image_bf16, (bf16_t*)out_bf16, rows, (int)S, (int)ps, ld_out);
+        hipLaunchKernelGGL(im2row_kernel<8>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)image_bf16, (bf16_t*)out_bf16, rows, (int)H, (int)W, (int)ps, ld_out);
     } else {
         const int64_t n = rows * 3 * ps * (ps / 2);
-        hipLaunchKernelGGL(im2row_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)image_bf16, (bf16_t*)out_bf16, rows, (int)S, (int)ps, ld_out);
+        hipLaunchKernelGGL(im2row_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)image_bf16, (bf16_t*)out_bf16, rows, (int)H, (int)W, (int)ps, ld_out);
     }
     OWL_LAUNCH_CHECK();
     return 0;
+}
+
+OWL_API int owl_im2row_bf16(void* stream, const void* image_bf16, void* out_bf16, int64_t ld_out, int64_t B, int64_t S, int64_t ps) {
+    return owl_im2row_bf16_hw(stream, image_bf16, out_bf16, ld_out, B, S, S, ps);
 }
 
 // out[r][c] (+)= sum_{s < nsplit} slabs[s * slab_stride + r * ld_slab + c], c < cols <= ld_slab: the slab reduction for a split-K product whose slabs carry pad

@@ -92,7 +92,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_nt_kernel(Gem
             if constexpr (PATCH) {
                 const int64_t b = am / p.P, pp = am - b * p.P;
                 const int64_t py = pp / p.G, px = pp - py * p.G;
-                a_src[q] = p.A + ((b * 3) * p.S + py * p.ps) * p.S + px * p.ps;   // + (ch*S + ky)*S + kx per K-step
+                a_src[q] = p.A + ((b * 3) * p.H + py * p.ps) * p.S + px * p.ps;   // + (ch*H + ky)*S + kx per K-step
             } else {
                 a_src[q] = p.A + am * p.lda + c * 8;
             }
@@ -129,7 +129,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_nt_kernel(Gem
                 const int k = kt * BK + c * 8;
                 const int ch = k >> (2 * p.ps_log2), rem = k & ((1 << (2 * p.ps_log2)) - 1);
                 const int ky = rem >> p.ps_log2, kx = rem & ((1 << p.ps_log2) - 1);
-                ga = a_src[q] + ((int64_t)ch * p.S + ky) * p.S + kx;
+                ga = a_src[q] + ((int64_t)ch * p.H + ky) * p.S + kx;
             } else {
                 ga = a_src[q] + (int64_t)kt * BK;
             }
@@ -494,10 +494,10 @@ OWL_API int owl_slab_reduce(void* stream, const float* slabs, float* out, int64_
 
 // Explicit im2row in the gather's K order (below) -- only for the single-phase REFERENCE kernels (tile = 256 / 128) on patch sizes that are not 2^n:
 // patches[b*P + p, (c*ps + ky)*psp + pos] = image[b, c, py*ps + ky, px*ps + min(8*(pos/8), ps - 8) + pos%8], zero-padded to Kg.
-__global__ __launch_bounds__(256) void im2row_kernel(const bf16_t* __restrict__ img, bf16_t* __restrict__ out, int64_t B, int S, int ps, int psp,
+// (image [B, 3, H, W]; P = gh * gw patches, p = py * gw + px)
+__global__ __launch_bounds__(256) void im2row_kernel(const bf16_t* __restrict__ img, bf16_t* __restrict__ out, int64_t P, int H, int S, int ps, int psp,
                                                      int G, int K, int Kg) {
     const int64_t row = blockIdx.x;                  // b*P + p
-    const int64_t P = (int64_t)G * G;
     const int64_t b = row / P; const int pp = (int)(row - b * P);
     const int py = pp / G, px = pp - py * G;
     for (int k = threadIdx.x; k < Kg; k += 256) {
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(256) void im2row_kernel(const bf16_t* __restrict__ 
         if (k < K) {
             const int r = k / psp, pos = k - r * psp, c = r / ps, ky = r - c * ps;
             const int kx = min((pos >> 3) << 3, ps - 8) + (pos & 7);
-            v = img[((b * 3 + c) * S + py * ps + ky) * (int64_t)S + px * ps + kx];
+            v = img[((b * 3 + c) * H + py * ps + ky) * (int64_t)S + px * ps + kx];
         }
         out[row * Kg + k] = v;
     }
@@ -526,32 +526,40 @@ static bool patch_embed_takes_pp2(int64_t M, int64_t D, int64_t Kg, int tile) {
 // Bytes of the `scratch` argument of owl_patch_embed_bf16 for this problem and kernel choice: 0 when the chosen kernel gathers from the image itself (every 2^n
 // patch size; any patch size on the ping-pong kernel), else the im2row matrix bf16 [B*P rounded up to 128 rows, Kg].  The ONE place the rule lives (ADVICE r05:
 // the Python side used to restate the dispatcher's predicate).
-OWL_API int owl_patch_embed_scratch_bytes(int64_t B, int64_t S, int64_t ps, int64_t D, int tile, int64_t* bytes) {
-    OWL_CHECK_ARG(bytes && B > 0 && ps >= 8 && ps <= 64 && ps % 2 == 0 && S > 0 && S % ps == 0 && D > 0, "owl_patch_embed_scratch_bytes: bad arguments");
-    const int64_t G = S / ps, P = G * G;
+OWL_API int owl_patch_embed_scratch_bytes_hw(int64_t B, int64_t H, int64_t W, int64_t ps, int64_t D, int tile, int64_t* bytes) {
+    OWL_CHECK_ARG(bytes && B > 0 && ps >= 8 && ps <= 64 && ps % 2 == 0 && H > 0 && H % ps == 0 && W > 0 && W % ps == 0 && D > 0, "owl_patch_embed_scratch_bytes: bad arguments");
+    const int64_t P = (H / ps) * (W / ps);
     int64_t psp = 8; while (psp < ps) psp *= 2;
     const int64_t Kg = (3 * ps * psp + BK - 1) / BK * BK;
     *bytes = (psp == ps || patch_embed_takes_pp2(B * P, D, Kg, tile)) ? 0 : ((B * P + 127) / 128 * 128) * Kg * 2;
     return 0;
 }
 
-OWL_API int owl_patch_embed_bf16(void* stream, const void* image_bf16, const void* w_pe, const float* pos,
-                                    float* x_out, void* scratch, int64_t B, int64_t S, int64_t ps, int64_t D, int64_t Tp, int tile) {
+OWL_API int owl_patch_embed_scratch_bytes(int64_t B, int64_t S, int64_t ps, int64_t D, int tile, int64_t* bytes) {
+    return owl_patch_embed_scratch_bytes_hw(B, S, S, ps, D, tile, bytes);
+}
+
+// The image is [B, 3, H, W]; patch p = py * gw + px (gh = H / ps, gw = W / ps: the order of conv2d(...).flatten(2)) lands in row b * Tp + 1 + p.  The gather's
+// row stride and patch-row divisor are W and gw, its channel stride H * W (GemmP.S / G / H); the square entry below is this one with H = W = S.
+OWL_API int owl_patch_embed_bf16_hw(void* stream, const void* image_bf16, const void* w_pe, const float* pos,
+                                       float* x_out, void* scratch, int64_t B, int64_t H, int64_t W, int64_t ps, int64_t D, int64_t Tp, int tile) {
     OWL_CHECK_ARG(image_bf16 && w_pe && pos && x_out, "owl_patch_embed_bf16: null pointer");
-    // (even patch sizes only: a 16-byte LDS-DMA piece starts at byte 2 * (row * S + px * ps + kx), which is 4-byte aligned -- what global_load_lds_dwordx4
-    //  needs -- only when ps, hence S, is even; tested: every even size 8 .. 64 on each kernel, bit for bit on integer data, with NaN patches, at an
-    //  8-byte-aligned image base and with byte offsets above 2^31 -- tests/test_embed_reference_gpu.py, profiles/embed_reference.md)
-    OWL_CHECK_ARG(S % ps == 0 && ps >= 8 && ps <= 64 && ps % 2 == 0, "owl_patch_embed_bf16: image side must be a multiple of the patch size, patch size even and 8 <= patch size <= 64");
-    const int64_t G = S / ps, P = G * G;
+    // (even patch sizes only: a 16-byte LDS-DMA piece starts at byte 2 * (row * W + px * ps + kx), which is 4-byte aligned -- what global_load_lds_dwordx4
+    //  needs -- only when ps, hence W, is even; tested: every even size 8 .. 64 on each kernel, bit for bit on integer data, with NaN patches, at an
+    //  8-byte-aligned image base and with byte offsets above 2^31 -- tests/test_embed_reference_gpu.py, profiles/embed_reference.md; rectangles:
+    //  tests/test_rect_kernels_gpu.py)
+    OWL_CHECK_ARG(ps >= 8 && ps <= 64 && ps % 2 == 0 && H > 0 && W > 0 && H % ps == 0 && W % ps == 0,
+                  "owl_patch_embed_bf16: image side must be a multiple of the patch size, patch size even and 8 <= patch size <= 64");
+    const int64_t G = W / ps, P = (H / ps) * G;
     int64_t psp = 8; while (psp < ps) psp *= 2;
     const int64_t K = 3 * ps * psp, Kg = (K + BK - 1) / BK * BK;
     OWL_CHECK_ARG(D % 8 == 0 && Tp >= P + 1, "owl_patch_embed_bf16: D %% 8, Tp");
-    OWL_CHECK_ARG(B * 3 * S * S * 2 < (1LL << 32) && B * P < (1LL << 31), "owl_patch_embed_bf16: image batch beyond 4 GiB (unsigned 32-bit gather byte offsets)");
+    OWL_CHECK_ARG(B > 0 && B * 3 * H * W * 2 < (1LL << 32) && B * P < (1LL << 31), "owl_patch_embed_bf16: image batch beyond 4 GiB (unsigned 32-bit gather byte offsets)");
     OWL_CHECK_ARG(tile == 0 || tile == 7 || tile == 256 || tile == 128, "owl_patch_embed_bf16: tile must be 0 (auto), 7, 256 or 128");
     const bool pow2 = psp == ps;
     GemmP p{};
     p.bias = nullptr; p.out = x_out; p.ldo = D; p.M = B * P; p.N = D; p.alpha = 1.f;
-    p.Tp = Tp; p.P = P; p.G = G; p.ps = ps; p.S = S; p.pos = pos;
+    p.Tp = Tp; p.P = P; p.G = G; p.ps = ps; p.S = W; p.H = H; p.pos = pos;
     p.W = (const bf16_t*)w_pe; p.w_rows = D; p.a_rows = B * P;
     p.ps_log2 = 0; while ((1LL << p.ps_log2) < psp) p.ps_log2++;
     p.ps_magic = (int)(65536 / ps + 1);
@@ -564,8 +572,13 @@ OWL_API int owl_patch_embed_bf16(void* stream, const void* image_bf16, const voi
     OWL_CHECK_ARG(scratch, "owl_patch_embed_bf16: patch size %lld on a single-phase kernel (tile %d, or a problem too small for the ping-pong kernel) needs the im2row scratch buffer",
                   (long long)ps, tile);
     hipLaunchKernelGGL(im2row_kernel, dim3((unsigned)(B * P)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)image_bf16, (bf16_t*)scratch,
-                       B, (int)S, (int)ps, (int)psp, (int)G, (int)K, (int)Kg);
+                       P, (int)H, (int)W, (int)ps, (int)psp, (int)G, (int)K, (int)Kg);
     OWL_LAUNCH_CHECK();
     p.A = (const bf16_t*)scratch; p.lda = Kg;
     return launch<EPI_PATCHM_F32>((hipStream_t)stream, p, 1, gemm_single_phase(p.M, D, tile));
+}
+
+OWL_API int owl_patch_embed_bf16(void* stream, const void* image_bf16, const void* w_pe, const float* pos,
+                                    float* x_out, void* scratch, int64_t B, int64_t S, int64_t ps, int64_t D, int64_t Tp, int tile) {
+    return owl_patch_embed_bf16_hw(stream, image_bf16, w_pe, pos, x_out, scratch, B, S, S, ps, D, Tp, tile);
 }

@@ -34,7 +34,8 @@ struct GemmP {
     int tiles_m, tiles_n, kt_per_split, nsplit, persistent;
     float alpha;
     int64_t Tp;            // EPI_TRANS: rows per image
-    int64_t P, G, ps, S;   // EPI_PATCH: patches / grid / patch size / image side
+    int64_t P, G, ps, S;   // EPI_PATCH: patches (gh * gw) / grid width gw / patch size / image width (the row stride)
+    int64_t H;             // EPI_PATCH: image height (the channel stride is H * S; = S for a square image)
     int ps_log2;           // log2 of the PADDED patch-row length psp (= ps for power-of-two patch sizes)
     int ps_magic;          // 65536 / ps + 1: R / ps == (R * ps_magic) >> 16 for the gather's row index R < 3 ps + 8 (patch sizes that are not 2^n)
     const float* pos;      // [T, N]

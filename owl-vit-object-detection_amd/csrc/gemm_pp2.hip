@@ -109,12 +109,12 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(GemmP p) {
                     int64_t am = m0 + r; if (am >= p.a_rows) am = p.a_rows - 1;
                     if constexpr (GATHER) {
                         // (32-bit arithmetic: the 64-bit divisions here cost 14 spilled VGPRs inside the K loop; unsigned byte offsets: the host checks that the image batch stays below 2^32 bytes, csrc/gemm.hip)
-                        const unsigned P32 = (unsigned)p.P, G32 = (unsigned)p.G, S32 = (unsigned)p.S, ps32 = (unsigned)p.ps;
+                        const unsigned P32 = (unsigned)p.P, G32 = (unsigned)p.G, S32 = (unsigned)p.S, H32 = (unsigned)p.H, ps32 = (unsigned)p.ps;   // (G = gw, S = W: patch p = py * gw + px, rows of W pixels, channels of H rows)
                         const unsigned b = (unsigned)am / P32, pp = (unsigned)am - b * P32;
                         const unsigned py = pp / G32, px = pp - py * G32;
                         unsigned ky = (unsigned)(c * 8) >> p.ps_log2, kx = (unsigned)(c * 8) & ((1u << p.ps_log2) - 1u);
                         if (np2) { a_j[q] = (int)ky; ky = 0; kx = min(kx, ps32 - 8u); }        // (row part added per K-tile; the last chunk overlaps instead of overrunning)
-                        a_voff[h][q] = ((((b * 3u) * S32 + py * ps32 + ky) * S32) + px * ps32 + kx) * 2u;
+                        a_voff[h][q] = ((((b * 3u) * H32 + py * ps32 + ky) * S32) + px * ps32 + kx) * 2u;
                     } else {
                         a_voff[h][q] = (unsigned)(((am - m0) * p.lda + c * 8) * 2);
                     }
@@ -131,12 +131,12 @@ __global__ __launch_bounds__(512) void gemm_pp2_kernel(GemmP p) {
                     unsigned R = (unsigned)(a_k * (QBK >> p.ps_log2) + a_j[q]);
                     R = min(R, 3u * (unsigned)p.ps - 1u);                     // (the K padding's rows: any row of the patch, their weights are zero)
                     const unsigned ch = (R * (unsigned)p.ps_magic) >> 16, ky = R - ch * (unsigned)p.ps;
-                    roff[q] = ((ch * (unsigned)p.S + ky) * (unsigned)p.S) * 2u;
+                    roff[q] = ((ch * (unsigned)p.H + ky) * (unsigned)p.S) * 2u;
                 }
             } else {
                 const int k = a_k * QBK;
                 const int ch = k >> (2 * p.ps_log2), ky = (k & ((1 << (2 * p.ps_log2)) - 1)) >> p.ps_log2;
-                koff = ((int64_t)ch * p.S + ky) * p.S;
+                koff = ((int64_t)ch * p.H + ky) * p.S;
             }
         }
         const unsigned char* g = (const unsigned char*)(a_base + koff);

@@ -1,4 +1,4 @@
-// Position table at another input size than the checkpoint's: U [g g + 1, D] = bicubic resample of the native table pos [g0 g0 + 1, D] (HF5:296-332
+// Position table at another input size than the checkpoint's: U [gh gw + 1, D] (row 1 + y gw + x) = bicubic resample of the native table pos [g0 g0 + 1, D] (HF5:296-332
 // `interpolate_pos_encoding` = torch.nn.functional.interpolate(mode="bicubic", align_corners=False) on the [g0, g0, D] patch rows; the class row is
 // copied), and its exact adjoint for a trainable table.  Run only by a model built at g != g0 (models.OwlViT); f32 in and out.
 // Both kernels evaluate the same per-axis taps (axis_taps below), in plain f32 with contraction off and explicit fmaf, so that the rounding count
@@ -34,7 +34,7 @@ __device__ __forceinline__ void axis_taps(int o, int g0, int g, int idx[4], floa
 // forward: one workgroup per row of U, one thread per 4 columns (16 bytes per lane, the row contiguous across the lanes).  The taps are the
 // same in every lane.  out[1 + y g + x] = sum_{i, j} fl(wy_i wx_j) pos[1 + cy_i g0 + cx_j], i outer, j inner, one fmaf per tap.
 // ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pos_resample_kernel(const float* __restrict__ pos, float* __restrict__ out, int g0, int g, int D) {
+__global__ __launch_bounds__(256) void pos_resample_kernel(const float* __restrict__ pos, float* __restrict__ out, int g0, int gh, int gw, int D) {
 #pragma clang fp contract(off)
     const int t = blockIdx.x;
     if (t == 0) {
@@ -43,8 +43,8 @@ __global__ __launch_bounds__(256) void pos_resample_kernel(const float* __restri
     }
     int iy[4], ix[4];
     float wy[4], wx[4];
-    axis_taps((t - 1) / g, g0, g, iy, wy);
-    axis_taps((t - 1) % g, g0, g, ix, wx);
+    axis_taps((t - 1) / gw, g0, gh, iy, wy);
+    axis_taps((t - 1) % gw, g0, gw, ix, wx);
     for (int c = threadIdx.x * 4; c < D; c += 1024) {
         float4 a = make_float4(0, 0, 0, 0);
 #pragma unroll
@@ -60,13 +60,17 @@ __global__ __launch_bounds__(256) void pos_resample_kernel(const float* __restri
     }
 }
 
-OWL_API int owl_pos_resample(void* stream, const float* pos, float* out, int64_t g0, int64_t g, int64_t D) {
+OWL_API int owl_pos_resample_hw(void* stream, const float* pos, float* out, int64_t g0, int64_t gh, int64_t gw, int64_t D) {
     OWL_CHECK_ARG(pos && out, "owl_pos_resample: null pointer");
-    OWL_CHECK_ARG(g0 >= 1 && g0 <= POS_MAX_GRID && g >= 1 && g <= POS_MAX_GRID && D >= 8 && D % 8 == 0 && D < (1 << 20),
+    OWL_CHECK_ARG(g0 >= 1 && g0 <= POS_MAX_GRID && gh >= 1 && gh <= POS_MAX_GRID && gw >= 1 && gw <= POS_MAX_GRID && D >= 8 && D % 8 == 0 && D < (1 << 20),
                   "owl_pos_resample: grids of side 1 .. 256, D a positive multiple of 8");
-    hipLaunchKernelGGL(pos_resample_kernel, dim3((unsigned)(g * g + 1)), dim3(256), 0, (hipStream_t)stream, pos, out, (int)g0, (int)g, (int)D);
+    hipLaunchKernelGGL(pos_resample_kernel, dim3((unsigned)(gh * gw + 1)), dim3(256), 0, (hipStream_t)stream, pos, out, (int)g0, (int)gh, (int)gw, (int)D);
     OWL_LAUNCH_CHECK();
     return 0;
+}
+
+OWL_API int owl_pos_resample(void* stream, const float* pos, float* out, int64_t g0, int64_t g, int64_t D) {
+    return owl_pos_resample_hw(stream, pos, out, g0, g, g, D);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -98,7 +102,7 @@ __device__ __forceinline__ float axis_weight_on(int o, int s, int g0, int g) {
     return m;
 }
 
-__global__ __launch_bounds__(256) void pos_resample_bwd_kernel(const float* __restrict__ dU, float* __restrict__ dpos, int g0, int g, int D) {
+__global__ __launch_bounds__(256) void pos_resample_bwd_kernel(const float* __restrict__ dU, float* __restrict__ dpos, int g0, int gh, int gw, int D) {
 #pragma clang fp contract(off)
     __shared__ float s_my[POS_MAX_GRID], s_mx[POS_MAX_GRID];
     const int cell = blockIdx.x;
@@ -113,16 +117,16 @@ __global__ __launch_bounds__(256) void pos_resample_bwd_kernel(const float* __re
     }
     const int sy = (cell - 1) / g0, sx = (cell - 1) % g0;
     int y_lo, y_hi, x_lo, x_hi;
-    touch_range(sy, g0, g, y_lo, y_hi);
-    touch_range(sx, g0, g, x_lo, x_hi);
-    for (int k = y_lo + threadIdx.x; k <= y_hi; k += 256) s_my[k] = axis_weight_on(k, sy, g0, g);
-    for (int k = x_lo + threadIdx.x; k <= x_hi; k += 256) s_mx[k] = axis_weight_on(k, sx, g0, g);
+    touch_range(sy, g0, gh, y_lo, y_hi);
+    touch_range(sx, g0, gw, x_lo, x_hi);
+    for (int k = y_lo + threadIdx.x; k <= y_hi; k += 256) s_my[k] = axis_weight_on(k, sy, g0, gh);
+    for (int k = x_lo + threadIdx.x; k <= x_hi; k += 256) s_mx[k] = axis_weight_on(k, sx, g0, gw);
     __syncthreads();
     for (int c = threadIdx.x * 4; c < D; c += 1024) {
         float4 a = make_float4(0, 0, 0, 0);
         for (int y = y_lo; y <= y_hi; y++) {
             const float my = s_my[y];
-            const float* row = dU + (int64_t)(1 + y * g) * D + c;
+            const float* row = dU + (int64_t)(1 + y * gw) * D + c;
             for (int x = x_lo; x <= x_hi; x++) {
                 const float m = my * s_mx[x];
                 const float4 v = *(const float4*)(row + (int64_t)x * D);
@@ -136,11 +140,15 @@ __global__ __launch_bounds__(256) void pos_resample_bwd_kernel(const float* __re
     }
 }
 
-OWL_API int owl_pos_resample_bwd(void* stream, const float* dU, float* dpos, int64_t g0, int64_t g, int64_t D) {
+OWL_API int owl_pos_resample_bwd_hw(void* stream, const float* dU, float* dpos, int64_t g0, int64_t gh, int64_t gw, int64_t D) {
     OWL_CHECK_ARG(dU && dpos, "owl_pos_resample_bwd: null pointer");
-    OWL_CHECK_ARG(g0 >= 1 && g0 <= POS_MAX_GRID && g >= 1 && g <= POS_MAX_GRID && D >= 8 && D % 8 == 0 && D < (1 << 20),
+    OWL_CHECK_ARG(g0 >= 1 && g0 <= POS_MAX_GRID && gh >= 1 && gh <= POS_MAX_GRID && gw >= 1 && gw <= POS_MAX_GRID && D >= 8 && D % 8 == 0 && D < (1 << 20),
                   "owl_pos_resample_bwd: grids of side 1 .. 256, D a positive multiple of 8");
-    hipLaunchKernelGGL(pos_resample_bwd_kernel, dim3((unsigned)(g0 * g0 + 1)), dim3(256), 0, (hipStream_t)stream, dU, dpos, (int)g0, (int)g, (int)D);
+    hipLaunchKernelGGL(pos_resample_bwd_kernel, dim3((unsigned)(g0 * g0 + 1)), dim3(256), 0, (hipStream_t)stream, dU, dpos, (int)g0, (int)gh, (int)gw, (int)D);
     OWL_LAUNCH_CHECK();
     return 0;
+}
+
+OWL_API int owl_pos_resample_bwd(void* stream, const float* dU, float* dpos, int64_t g0, int64_t g, int64_t D) {
+    return owl_pos_resample_bwd_hw(stream, dU, dpos, g0, g, g, D);
 }

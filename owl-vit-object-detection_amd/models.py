@@ -26,19 +26,20 @@ from .postprocess import PostProcess  # noqa: F401  (the reference exports it fr
 from .prefix_cache import PrefixCache, _id_list
 
 
-def box_bias_table(grid: int) -> torch.Tensor:
-    """HF5:1071-1104 `compute_box_bias` for a square grid (computed once on the host, as HF keeps
-    it as a buffer): [P,4] f32, p = y*W + x."""
-    coords = torch.arange(1, grid + 1, dtype=torch.float32)
-    xx, yy = torch.meshgrid(coords, coords, indexing="xy")
+def box_bias_table(grid: int, grid_w: int = None) -> torch.Tensor:
+    """HF5:1071-1104 `compute_box_bias(num_patches_height, num_patches_width)` (computed once on the host, as HF keeps
+    it as a buffer): [P,4] f32, p = y*gw + x.  box_bias_table(g) is the square g x g table; box_bias_table(gh, gw) divides x by gw and y by gh and
+    biases the width by 1 / gw and the height by 1 / gh."""
+    gh, gw = grid, (grid if grid_w is None else grid_w)
+    xx, yy = torch.meshgrid(torch.arange(1, gw + 1, dtype=torch.float32), torch.arange(1, gh + 1, dtype=torch.float32), indexing="xy")
     bc = torch.stack((xx, yy), dim=-1)
-    bc[..., 0] /= grid
-    bc[..., 1] /= grid
+    bc[..., 0] /= gw
+    bc[..., 1] /= gh
     bc = torch.clip(bc.view(-1, 2), 0.0, 1.0)
     coord_bias = torch.log(bc + 1e-4) - torch.log1p(-bc + 1e-4)
     size = torch.full_like(coord_bias, 1.0)
-    size[..., 0] /= grid
-    size[..., 1] /= grid
+    size[..., 0] /= gw
+    size[..., 1] /= gh
     size_bias = torch.log(size + 1e-4) - torch.log1p(-size + 1e-4)
     return torch.cat([coord_bias, size_bias], dim=-1).contiguous()
 
@@ -92,7 +93,7 @@ class OwlViT(nn.Module):
         super().__init__()
         self.cfg = cfg
         if cfg.pos_grid:
-            check_image_size(cfg.image_size, cfg.patch_size, cfg.pos_rows)
+            check_image_size(cfg.image_size, cfg.patch_size, cfg.pos_rows)          # (an int or a pair, as the config holds it)
         self.device_ = torch.device(device)
         if cfg.head_dim != 64:
             raise ValueError("attention kernels are built for head_dim = 64")
@@ -191,11 +192,11 @@ class OwlViT(nn.Module):
                     self._fz[n] = P_[n].to(torch.bfloat16).contiguous()
                     if self.backward_floor != "heads":
                         self._fz[n + ".T"] = self._fz[n].t().contiguous()
-        self.box_bias = box_bias_table(cfg.grid).to(self.device_)
+        self.box_bias = box_bias_table(cfg.grid_h, cfg.grid_w).to(self.device_)
         # run grid != native grid: the embeddings read `_pos_used` [T, D], the native table resampled (the parameter keeps its native shape).  Frozen
         # embeddings: made here and after every load_state_dict; trainable ones: by every forward (_forward_impl).  At the native size nothing of this exists.
         self._pos_used = None
-        if cfg.native_grid != cfg.grid:
+        if cfg.resampled:                  # (by the grid's two sides, not by P: 4 x 9 has the 36 patches of a native 6 x 6 table)
             self._pos_used = torch.zeros(cfg.tokens, D, dtype=torch.float32, device=self.device_)
             self._refresh_pos()
             self.register_load_state_dict_post_hook(lambda module, incompatible: module._refresh_pos())
@@ -320,7 +321,7 @@ class OwlViT(nn.Module):
         not 2^n on a problem too small for the ping-pong kernel needs one; L/14 at any batch size does not."""
         cfg = self.cfg
         nbytes = torch.zeros(1, dtype=torch.int64)
-        _lib.call("owl_patch_embed_scratch_bytes", B, cfg.image_size, cfg.patch_size, cfg.hidden, 0, nbytes)
+        _lib.call("owl_patch_embed_scratch_bytes_hw", B, *cfg.image_hw, cfg.patch_size, cfg.hidden, 0, nbytes)
         if int(nbytes.item()) == 0:
             return None
         key = ("im2row", B)
@@ -357,7 +358,7 @@ class OwlViT(nn.Module):
             # query table: [32, Dt] (<= 10 classes: one MFMA tile), or the wide head's [nblk][32][Dt] blocks of 10 classes (csrc/class_head_wide.hip)
             qhat=torch.zeros(nqr, Dt, device=dev), qnorm=torch.zeros(nqr, device=dev),
             argmax=torch.zeros(Mh, C, dtype=torch.uint8, device=dev), inv_norm=torch.zeros(Mh, device=dev),
-            img=torch.zeros(B, 3, cfg.image_size, cfg.image_size, dtype=bf, device=dev),
+            img=torch.zeros(B, 3, *cfg.image_hw, dtype=bf, device=dev),
             gen=0,          # set from the model-global counter by every recording forward (_forward_impl)
         )
         self._ws[key] = ws
@@ -447,7 +448,7 @@ class OwlViT(nn.Module):
         self._invalidate_prefix()          # (a frozen table re-made: what the kept states were computed from may have changed)
         if self._pos_used is not None:
             cfg = self.cfg
-            ops.pos_resample(self._byname[_POS].detach(), self._pos_used, cfg.native_grid, cfg.grid, cfg.hidden)
+            ops.pos_resample_hw(self._byname[_POS].detach(), self._pos_used, cfg.native_grid, cfg.grid_h, cfg.grid_w, cfg.hidden)
 
     def _pos_table(self):
         """The position table at the run grid: the parameter itself at the native size."""
@@ -652,8 +653,8 @@ class OwlViT(nn.Module):
         cfg = self.cfg
         D, I, H, Tp, T, P, Dt, C = cfg.hidden, cfg.mlp, cfg.heads, cfg.tokens_padded, cfg.tokens, cfg.patches, cfg.text_dim, cfg.n_classes
         B = image.shape[0] if ids is None else len(ids)
-        if image is not None and tuple(image.shape[1:]) != (3, cfg.image_size, cfg.image_size):
-            raise ValueError(f"image must be [B,3,{cfg.image_size},{cfg.image_size}], got {tuple(image.shape)}")
+        if image is not None and tuple(image.shape[1:]) != (3, *cfg.image_hw):
+            raise ValueError(f"image must be [B,3,{cfg.image_hw[0]},{cfg.image_hw[1]}], got {tuple(image.shape)}")
         plan = None
         if ids is not None:
             cache = self.prefix_cache
@@ -710,13 +711,13 @@ class OwlViT(nn.Module):
             if self._train_emb and img is not ws["img"]:
                 ws["img"].copy_(img)
             x_emb = pw["x_emb"]
-            ops.patch_embed(img, self._fz["w_pe"], pos, x_emb, B, cfg.image_size,
-                            cfg.patch_size, D, Tp, scratch=self._patch_scratch(B))
+            ops.patch_embed_hw(img, self._fz["w_pe"], pos, x_emb, B, *cfg.image_hw,
+                               cfg.patch_size, D, Tp, scratch=self._patch_scratch(B))
             ops.cls_rows(x_emb, P_["backbone.embeddings.class_embedding"], pos, B, Tp, D)
             ops.layernorm(x_emb, P_["backbone.pre_layernorm.weight"], P_["backbone.pre_layernorm.bias"], x, M, D, pw["st_pre"], cfg.ln_eps)
         else:
-            ops.patch_embed(img, self._fz["w_pe"], pos, x, Bp, cfg.image_size,
-                            cfg.patch_size, D, Tp, scratch=self._patch_scratch(Bp))
+            ops.patch_embed_hw(img, self._fz["w_pe"], pos, x, Bp, *cfg.image_hw,
+                               cfg.patch_size, D, Tp, scratch=self._patch_scratch(Bp))
             ops.cls_rows(x, P_["backbone.embeddings.class_embedding"], pos, Bp, Tp, D)
             ops.layernorm(x, P_["backbone.pre_layernorm.weight"], P_["backbone.pre_layernorm.bias"], x, Bp * Tp, D, eps=cfg.ln_eps)
 
@@ -1133,9 +1134,9 @@ def text_queries(who, B, input_ids, text_tower, shared=None):
 def check_detect_args(cfg, pixel_values, query_embeds, query_mask=None):
     """Host-side validation of OwlViT.detect's arguments (shapes and dtypes only: no device is touched) -> (B, Q, shared bank?).  ValueError names
     the expected shape."""
-    if not hasattr(pixel_values, "shape") or len(pixel_values.shape) != 4 or tuple(pixel_values.shape[1:]) != (3, cfg.image_size, cfg.image_size) \
+    if not hasattr(pixel_values, "shape") or len(pixel_values.shape) != 4 or tuple(pixel_values.shape[1:]) != (3, *cfg.image_hw) \
             or pixel_values.shape[0] < 1:
-        raise ValueError(f"detect: pixel_values must be [B, 3, {cfg.image_size}, {cfg.image_size}] with B >= 1, got {tuple(getattr(pixel_values, 'shape', ()))}")
+        raise ValueError(f"detect: pixel_values must be [B, 3, {cfg.image_hw[0]}, {cfg.image_hw[1]}] with B >= 1, got {tuple(getattr(pixel_values, 'shape', ()))}")
     B, Dt = int(pixel_values.shape[0]), cfg.text_dim
     qe = torch.as_tensor(query_embeds)
     if qe.dim() not in (2, 3) or qe.shape[-1] != Dt or (qe.dim() == 3 and qe.shape[0] != B):
@@ -1219,7 +1220,8 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
 
     `trainable` (None = the reference's freeze rule): the substring list of that rule, as a user of the reference would edit it -- see OwlViT.
 
-    `image_size` (None = the architecture's): the square input size the model is built for, a multiple of the patch size with at most 8192 patches
+    `image_size` (None = the architecture's): the input size the model is built for, an int (square) or a pair (height, width); each side a multiple of
+    the patch size, at most 8192 patches and 256 patches per side
     (HF's `interpolate_pos_encoding=True`, HF5:296-332).  The native grid of the position table is read off `state`'s table (a checkpoint's, through
     weights.from_hf_state_dict) or is the architecture's; the parameter keeps that shape and the embeddings read a bicubic resample of it, so
     state dicts and FusedAdamW states move freely between sizes.  At the native size nothing changes.
@@ -1236,9 +1238,9 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
     cfg = get_config(arch, n_classes=n_classes)
     g0 = table_grid(np.asarray(state[_POS]).shape[0]) if (state is not None and _POS in state) else cfg.grid
     if image_size is not None or g0 != cfg.grid:
-        S = cfg.image_size if image_size is None else int(image_size)
+        S = cfg.image_size if image_size is None else (tuple(int(v) for v in image_size) if isinstance(image_size, (tuple, list)) else int(image_size))
         g = check_image_size(S, cfg.patch_size, g0 * g0 + 1)
-        cfg = cfg.replace(image_size=S, pos_grid=0 if g0 == g else g0)
+        cfg = cfg.replace(image_size=S, pos_grid=0 if g in (g0, (g0, g0)) else g0)
     if (vocab is None) != (merges is None):
         raise ValueError("load_model: vocab= and merges= go together (the CLIP vocab.json and merges.txt)")
     if vocab is not None:

@@ -71,6 +71,13 @@ def patch_embed(image_bf16, w_pe, pos, x_out, B, S, ps, D, Tp, scratch=None, til
     _lib.call("owl_patch_embed_bf16", stream(), image_bf16, w_pe, pos, x_out, scratch, B, S, ps, D, Tp, int(tile))
 
 
+def patch_embed_hw(image_bf16, w_pe, pos, x_out, B, H, W, ps, D, Tp, scratch=None, tile=0):
+    """patch_embed on an image [B, 3, H, W]: patch y * (W / ps) + x goes to row b * Tp + 1 + p (the same kernels; H == W is patch_embed, bit for bit)."""
+    _chk(image_bf16, torch.bfloat16, "image"); _chk(w_pe, torch.bfloat16, "w_pe"); _chk(pos, torch.float32, "pos")
+    _chk(x_out, torch.float32, "x_out")
+    _lib.call("owl_patch_embed_bf16_hw", stream(), image_bf16, w_pe, pos, x_out, scratch, B, H, W, ps, D, Tp, int(tile))
+
+
 def cls_rows(x, cls, pos, B, Tp, D):
     _lib.call("owl_cls_rows", stream(), x, cls, pos, B, Tp, D)
 
@@ -544,12 +551,37 @@ def pos_resample_bwd(dU, dpos, g0, g, D):
     _lib.call("owl_pos_resample_bwd", stream(), dU, dpos, g0, g, D)
 
 
+def pos_resample_hw(pos, out, g0, gh, gw, D):
+    """pos_resample onto a rectangular grid: out [gh gw + 1, D], row 1 + y gw + x (HF's interpolate(size=(gh, gw)); gh == gw is pos_resample, bit for bit)."""
+    _chk(pos, torch.float32, "pos"); _chk(out, torch.float32, "out")
+    if pos.numel() < (g0 * g0 + 1) * D or out.numel() < (gh * gw + 1) * D:
+        raise ValueError("pos_resample_hw: pos must hold [g0 g0 + 1, D], out [gh gw + 1, D]")
+    _lib.call("owl_pos_resample_hw", stream(), pos, out, g0, gh, gw, D)
+    return out
+
+
+def pos_resample_bwd_hw(dU, dpos, g0, gh, gw, D):
+    """The adjoint of pos_resample_hw: dpos [g0 g0 + 1, D] += K^T dU [gh gw + 1, D]."""
+    _chk(dU, torch.float32, "dU"); _chk(dpos, torch.float32, "dpos")
+    if dU.numel() < (gh * gw + 1) * D or dpos.numel() < (g0 * g0 + 1) * D:
+        raise ValueError("pos_resample_bwd_hw: dU must hold [gh gw + 1, D], dpos [g0 g0 + 1, D]")
+    _lib.call("owl_pos_resample_bwd_hw", stream(), dU, dpos, g0, gh, gw, D)
+
+
 def im2row_bf16(image, out, B, S, ps):
     """out [>= B (S / ps)^2, ld] bf16 <- patches of image [B, 3, S, S] bf16, columns in the conv weight's (c, i, j) order; columns past 3 ps^2 are left alone."""
     _chk(image, torch.bfloat16, "image"); _chk(out, torch.bfloat16, "out")
     if image.numel() < B * 3 * S * S or out.dim() != 2 or out.shape[0] < B * (S // ps) ** 2:
         raise ValueError("im2row_bf16: image must hold [B, 3, S, S], out [>= B (S / ps)^2, ld]")
     _lib.call("owl_im2row_bf16", stream(), image, out, out.shape[1], B, S, ps)
+
+
+def im2row_bf16_hw(image, out, B, H, W, ps):
+    """im2row_bf16 on an image [B, 3, H, W]: out [>= B (H / ps) (W / ps), ld], row (b gh + gy) gw + gx."""
+    _chk(image, torch.bfloat16, "image"); _chk(out, torch.bfloat16, "out")
+    if image.numel() < B * 3 * H * W or out.dim() != 2 or out.shape[0] < B * (H // ps) * (W // ps):
+        raise ValueError("im2row_bf16_hw: image must hold [B, 3, H, W], out [>= B (H / ps) (W / ps), ld]")
+    _lib.call("owl_im2row_bf16_hw", stream(), image, out, out.shape[1], B, H, W, ps)
 
 
 def attention_bwd(qkv, dO, O, lse, dvec, dqkv, B, H, T, Tp, scale, phases=0):

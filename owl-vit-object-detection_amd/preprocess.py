@@ -29,12 +29,37 @@ def normalize_lut(mean, std, rescale_factor) -> np.ndarray:
     return ((v[None, :] - m) / s).astype(np.float32)
 
 
+def size_hw(size):
+    """(H, W) of a `size` given as an int (square) or a pair (height, width)."""
+    if isinstance(size, (tuple, list)):
+        if len(size) != 2:
+            raise ValueError(f"size={size!r}: an int (square) or a pair (height, width)")
+        return int(size[0]), int(size[1])
+    return int(size), int(size)
+
+
+def _size_attr(size):
+    """What the `size` attribute holds: the int for a square (a square pair included), else the pair (H, W)."""
+    H, W = size_hw(size)
+    if H < 1 or W < 1:
+        raise ValueError(f"size={size!r}: both sides must be positive")
+    return H if H == W else (H, W)
+
+
+_SQUARE_ONLY = ("{what} takes a square size: crop / flip / mosaic canvases, colour jitter and slices are built for S x S model inputs and the size "
+                "here is {size} (height, width).  The plain path -- __call__, normalize_sized, DevicePrefetcher without augment= -- runs at a rectangular size")
+
+
 class DeviceImageProcessor:
+    """`size`: the model's input size, an int (square) or a pair (height, width).  The plain path (__call__: Pillow's resize of each image to H x W plus the
+    table; normalize_sized) runs at either; the tile paths (run_tiles / tiles / slices) are square only and raise ValueError on a rectangle."""
+
     def __init__(self, size=768, image_mean=CLIP_MEAN, image_std=CLIP_STD, rescale_factor=1 / 255, device="cuda",
                  dtype=torch.float32):
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("DeviceImageProcessor: dtype must be torch.float32 or torch.bfloat16")
-        self.size = int(size)
+        self.size = _size_attr(size)         # the int for a square, (H, W) for a rectangle
+        self.hw = size_hw(size)
         self.device = torch.device(device)
         self.dtype = dtype
         self.lut = torch.from_numpy(normalize_lut(image_mean, image_std, rescale_factor)).to(self.device)
@@ -42,10 +67,13 @@ class DeviceImageProcessor:
         self._tmp = None
         self._ws = None                      # partial sums of the colour path (owl_preprocess_color_workspace_bytes)
 
-    def _axis_tables(self, in_size: int):
-        key = in_size
+    def _square(self, what: str):
+        if isinstance(self.size, tuple):
+            raise ValueError(_SQUARE_ONLY.format(what=what, size=self.size))
+
+    def _axis_tables(self, in_size: int, out: int):
+        key = (in_size, out)
         if key not in self._tables:
-            out = self.size
             ksize = int(math.ceil(2.0 * max(in_size / out, 1.0))) * 2 + 1
             bounds = torch.zeros(out * 2, dtype=torch.int32)
             kk = torch.zeros(out * ksize, dtype=torch.int32)
@@ -68,21 +96,22 @@ class DeviceImageProcessor:
         single = not isinstance(images, (list, tuple))
         imgs = [self._to_device(im) for im in ([images] if single else list(images))]
         n = len(imgs)
-        out = torch.empty(n, 3, self.size, self.size, dtype=self.dtype, device=self.device)
+        out_h, out_w = self.hw
+        out = torch.empty(n, 3, out_h, out_w, dtype=self.dtype, device=self.device)
         # one launch pair for the whole (ragged) batch: a 10-int64 descriptor per image
         rows, off, max_h = [], 0, 0
         for im in imgs:
             H, W = int(im.shape[0]), int(im.shape[1])
-            bx, kx, ksx = self._axis_tables(W)
-            by, ky, ksy = self._axis_tables(H)
+            bx, kx, ksx = self._axis_tables(W, out_w)
+            by, ky, ksy = self._axis_tables(H, out_h)
             rows.append((im.data_ptr(), H, W, bx.data_ptr(), kx.data_ptr(), ksx, by.data_ptr(), ky.data_ptr(), ksy, off))
-            off += (H * self.size * 3 + 255) // 256 * 256
+            off += (H * out_w * 3 + 255) // 256 * 256          # the horizontal pass's u8 intermediate: the image's H rows of out_w pixels
             max_h = max(max_h, H)
         if self._tmp is None or self._tmp.numel() < off:
             self._tmp = torch.empty(off, dtype=torch.uint8, device=self.device)
         desc_d = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(self.device, non_blocking=True)
         _lib.call("owl_preprocess_u8_batch", ops.stream(), desc_d, n, max_h, self._tmp, self.lut, out,
-                  1 if self.dtype == torch.bfloat16 else 0, self.size, self.size)
+                  1 if self.dtype == torch.bfloat16 else 0, out_h, out_w)
         self._keep = (imgs, desc_d)          # keep the sources alive until the stream has consumed them
         return {"pixel_values": out}
 
@@ -90,6 +119,7 @@ class DeviceImageProcessor:
         """Launch owl_preprocess_u8_tiles on the current stream for descriptors that are already on the device with absolute addresses (`build_tile_tables` +
         `resolve_tile_descs`) and whose cover the caller has checked (`check_tile_cover`) -> [n_out,3,S,S] self.dtype.  `color`: a DEVICE f32 [n_tiles,4] array of
         (fb, fc, fs, order) rows the caller has checked (`check_color`) -> owl_preprocess_u8_tiles_color instead; None: the plain launch pair, as ever."""
+        self._square("DeviceImageProcessor.run_tiles")
         if self._tmp is None or self._tmp.numel() < tmp_bytes:
             self._tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=self.device)
         out = torch.empty(n_out, 3, self.size, self.size, dtype=self.dtype, device=self.device)
@@ -111,6 +141,7 @@ class DeviceImageProcessor:
         Pillow's `resize((cw, ch), BICUBIC, box=...)`, `transpose(FLIP_LEFT_RIGHT)` and `paste`, bit for bit, in one launch pair.  Raises ValueError unless
         the cells of every output image cover it exactly.  `color` (host, [n_tiles,4] rows of (fb, fc, fs, order): `ColorJitter.sample`, `check_color`) puts
         Pillow's `ImageEnhance.Brightness / Contrast / Color` on each resized cell, in the row's order, between the resize and the table."""
+        self._square("DeviceImageProcessor.tiles")
         imgs = [self._to_device(im) for im in images]
         shapes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
         tiles = list(tiles)
@@ -130,6 +161,7 @@ class DeviceImageProcessor:
         """Sliced inference's input: every window of `slice_plan` resampled to one size x size canvas -> (pixel_values [T,3,S,S], plan).  A slice is a tile
         whose cell is the whole canvas, so this is `tiles()` unchanged and each canvas is Pillow's `resize((S, S), BICUBIC, box=window)` followed by the
         table.  `slice_size=None`: windows of the processor's own size (one model pixel per source pixel)."""
+        self._square("DeviceImageProcessor.slices")
         imgs = [self._to_device(im) for im in (list(images) if isinstance(images, (list, tuple)) else [images])]
         shapes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
         plan = slice_plan(shapes, self.size if slice_size is None else slice_size, overlap, full_image, size=self.size)
@@ -142,10 +174,10 @@ class DeviceImageProcessor:
             raise ValueError(f"normalize_sized: expected a device uint8 [B,S,S,3] / [B,3,S,S] tensor, got {src_u8.dtype} {tuple(src_u8.shape)} on {src_u8.device}")
         n = int(src_u8.shape[0])
         H, W_ = (int(src_u8.shape[2]), int(src_u8.shape[3])) if chw else (int(src_u8.shape[1]), int(src_u8.shape[2]))
-        if (int(src_u8.shape[1]) if chw else int(src_u8.shape[3])) != 3 or (H, W_) != (self.size, self.size):
-            raise ValueError(f"normalize_sized: expected {self.size} x {self.size} RGB images, got {tuple(src_u8.shape)} (chw={chw})")
+        if (int(src_u8.shape[1]) if chw else int(src_u8.shape[3])) != 3 or (H, W_) != self.hw:
+            raise ValueError(f"normalize_sized: expected {self.hw[0]} x {self.hw[1]} RGB images, got {tuple(src_u8.shape)} (chw={chw})")
         src_u8 = src_u8.contiguous()
-        out = torch.empty(n, 3, self.size, self.size, dtype=self.dtype, device=self.device)
+        out = torch.empty(n, 3, H, W_, dtype=self.dtype, device=self.device)
         _lib.call("owl_normalize_u8", ops.stream(), src_u8, 1 if chw else 0, self.lut, out, 1 if self.dtype == torch.bfloat16 else 0, n, H, W_)
         return out
 
@@ -445,7 +477,9 @@ class TrainAugment:
 
     def __init__(self, size, *, mosaic=(1,), scale=(0.3, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, min_visibility=0.3, min_box=2.0, seed=0, rank=0, max_tries=10,
                  color=None):
-        self.size = int(size)
+        if isinstance(size, (tuple, list)) and len(set(size_hw(size))) > 1:
+            raise ValueError(_SQUARE_ONLY.format(what="TrainAugment", size=tuple(size)))
+        self.size = _size_attr(size)
         self.mosaic = tuple(int(g) for g in mosaic)
         if not self.mosaic or any(g < 1 or self.size % g for g in self.mosaic):
             raise ValueError(f"TrainAugment: every mosaic grid must be >= 1 and divide size = {self.size}, got {mosaic}")
@@ -556,25 +590,27 @@ def _as_u8_tensor(img):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(img.convert("RGB") if hasattr(img, "convert") else img)))
 
 
-def classify_images(images, size: int):
-    """What a host batch's image part is -> (kind, items).  kind: 'dense' (f32 / bf16 [B,3,S,S] pixel_values, the reference DataLoader's output: copied, cast to
+def classify_images(images, size):
+    """`size`: the model's input size, an int S or a pair (H, W); below S x S stands for H x W.
+    What a host batch's image part is -> (kind, items).  kind: 'dense' (f32 / bf16 [B,3,S,S] pixel_values, the reference DataLoader's output: copied, cast to
     the compute type on the device), 'u8_chw' / 'u8_hwc' (uint8 [B,3,S,S] / [B,S,S,3] already at the model's size: table step only), 'u8_ragged' (a list of -- or
     a [B,H,W,3] tensor of -- uint8 HWC images of any sizes: Pillow-exact bicubic resize + table on the device).  Pure host logic (CPU-tested)."""
+    H, W = size_hw(size)
     if isinstance(images, (list, tuple)):
         items = [_as_u8_tensor(im) for im in images]
         if not items:
             raise ValueError("DevicePrefetcher: empty image list")
         if all(t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3 for t in items):
             return "u8_ragged", items
-        if all(t.dtype in (torch.float32, torch.bfloat16) and tuple(t.shape) == (3, size, size) for t in items):
+        if all(t.dtype in (torch.float32, torch.bfloat16) and tuple(t.shape) == (3, H, W) for t in items):
             return "dense", [torch.stack(items)]
         raise ValueError("DevicePrefetcher: a list of images must hold uint8 [H,W,3] images (or [3,S,S] pixel_values)")
     t = images if torch.is_tensor(images) else _as_u8_tensor(images)
     if t.dtype in (torch.float32, torch.bfloat16):
         if t.dim() == 3:
             t = t.unsqueeze(0)
-        if t.dim() != 4 or tuple(t.shape[1:]) != (3, size, size):
-            raise ValueError(f"DevicePrefetcher: pixel_values must be [B,3,{size},{size}], got {tuple(t.shape)}")
+        if t.dim() != 4 or tuple(t.shape[1:]) != (3, H, W):
+            raise ValueError(f"DevicePrefetcher: pixel_values must be [B,3,{H},{W}], got {tuple(t.shape)}")
         return "dense", [t]
     if t.dtype != torch.uint8:
         raise TypeError(f"DevicePrefetcher: images must be uint8 (raw pixels) or float32 / bfloat16 (pixel_values), got {t.dtype}")
@@ -582,10 +618,10 @@ def classify_images(images, size: int):
         t = t.unsqueeze(0)
     if t.dim() != 4:
         raise ValueError(f"DevicePrefetcher: uint8 images must be [B,H,W,3] or [B,3,S,S], got {tuple(t.shape)}")
-    if tuple(t.shape[1:]) == (3, size, size):
+    if tuple(t.shape[1:]) == (3, H, W):
         return "u8_chw", [t]
     if t.shape[3] == 3:
-        if tuple(t.shape[1:3]) == (size, size):
+        if tuple(t.shape[1:3]) == (H, W):
             return "u8_hwc", [t]
         return "u8_ragged", [t[i] for i in range(t.shape[0])]
     raise ValueError(f"DevicePrefetcher: cannot interpret a uint8 tensor of shape {tuple(t.shape)}")
@@ -652,7 +688,7 @@ class DevicePrefetcher:
             raise ValueError("DevicePrefetcher: the device must be a GPU (there is no CPU path)")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        self.size = int(size)
+        self.size = _size_attr(size)       # the int for a square, (H, W) for a rectangle (plain path only: augment= is square)
         self.dtype = dtype
         self.depth = max(1, int(depth))
         self.processor = processor if processor is not None else DeviceImageProcessor(size=size, device=self.device, dtype=dtype)
@@ -672,6 +708,8 @@ class DevicePrefetcher:
         self.batches = 0
         self.stage_seconds = 0.0           # host time spent staging (pull from the loader excluded): must stay below the step time for the stage to hide
         self.augment = augment
+        if augment is not None and isinstance(self.size, tuple):
+            raise ValueError(_SQUARE_ONLY.format(what="DevicePrefetcher(augment=)", size=self.size))
         if augment is not None and augment.size != self.size:
             raise ValueError(f"DevicePrefetcher: augment.size = {augment.size} but size = {self.size}")
         self.augment_seconds = 0.0         # of which: drawing the tiles and building their tap tables and descriptors

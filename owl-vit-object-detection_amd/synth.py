@@ -12,11 +12,11 @@ CLIP_STD = np.array([0.26862954, 0.26130258, 0.27577711], dtype=np.float64)
 
 
 def make_images(cfg: OwlConfig, batch: int, seed: int = 1234, first: int = 0) -> np.ndarray:
-    """[B,3,S,S] float32: u8 ~ U{0..255} -> /255 -> (x - mean) / std."""
-    S = cfg.image_size
-    out = np.empty((batch, 3, S, S), dtype=np.float32)
+    """[B,3,H,W] float32 (cfg.image_hw; [B,3,S,S] for a square config): u8 ~ U{0..255} -> /255 -> (x - mean) / std."""
+    H, W = cfg.image_hw
+    out = np.empty((batch, 3, H, W), dtype=np.float32)
     for b in range(batch):
-        u8 = rng.randint(seed, f"image/{first + b}", 3 * S * S, 256).reshape(3, S, S)
+        u8 = rng.randint(seed, f"image/{first + b}", 3 * H * W, 256).reshape(3, H, W)
         x = u8.astype(np.float64) / 255.0
         out[b] = ((x - CLIP_MEAN[:, None, None]) / CLIP_STD[:, None, None]).astype(np.float32)
     return out
@@ -26,10 +26,10 @@ def make_images_u8(cfg: OwlConfig, batch: int, seed: int = 1234, first: int = 0,
     """The uint8 levels make_images() normalises (the same draws), as a camera / decoder hands them over: [B,S,S,3] (`hwc`) or [B,3,S,S] (`chw`).
     What the u8 input stage (preprocess.DevicePrefetcher) is fed with; its table step gives make_images()'s values to within one f32 ulp (the HF
     processor rounds x/255 to f32 before normalising, make_images() normalises in f64)."""
-    S = cfg.image_size
-    out = np.empty((batch, 3, S, S), dtype=np.uint8)
+    H, W = cfg.image_hw
+    out = np.empty((batch, 3, H, W), dtype=np.uint8)
     for b in range(batch):
-        out[b] = rng.randint(seed, f"image/{first + b}", 3 * S * S, 256).reshape(3, S, S).astype(np.uint8)
+        out[b] = rng.randint(seed, f"image/{first + b}", 3 * H * W, 256).reshape(3, H, W).astype(np.uint8)
     return out if layout == "chw" else np.ascontiguousarray(out.transpose(0, 2, 3, 1))
 
 
