@@ -63,7 +63,7 @@ def test_compaction_edge_cases(rows):
 def _dense_tail(c, rows, D):
     """The dense kernel on the same inputs: du1 bf16 [rows, D], (dW2 | db2) f32, colsum f32."""
     du1 = torch.zeros(ops.pad_rows(rows), D, dtype=bf, device=DEV)
-    part = torch.zeros(_lib.load().owl_box_final_bwd_blocks(rows), 5 * D + 4, device=DEV)
+    part = torch.full((_lib.load().owl_box_final_bwd_blocks(rows), 5 * D + 4), float("nan"), device=DEV)          # scratch: NaN, so a word read before it is written shows
     g, cs = torch.zeros(4 * D + 4, device=DEV), torch.zeros(D, device=DEV)
     ops.box_final_bwd(c["dboxes"], c["sig"], c["hb1"], c["ub1"], c["w2"], du1, part, g, rows, D, du1_colsum=cs)
     return du1, g, cs

@@ -231,7 +231,7 @@ def test_box_final_backward(rows, D, profile):
     fails, runs = [], []
     for poison, with_cs in (("finite", True), ("nan", True), ("nan", False)):
         du1 = _out(rows, D, torch.bfloat16)
-        part = torch.zeros(nblk, 5 * D + 4, device=DEV)
+        part = torch.full((nblk, 5 * D + 4), float("nan"), device=DEV)          # the scratch need not be initialised: NaN, so a word read before it is written shows
         g = torch.cat([old["dW2"].reshape(-1), old["db2"]]).to(DEV)
         cs = old["colsum"].to(DEV).clone() if with_cs else None
         ops.box_final_bwd(_in(inp["dboxes"], poison), _in(inp["sig"], poison), _in(inp["h1"], poison, torch.bfloat16), _in(inp["u1"], poison, torch.bfloat16),

@@ -381,7 +381,7 @@ def test_box_final_bwd_matches_torch_autograd(rows, D):
     sig = s.detach().contiguous()
     du1 = torch.zeros(rows, D, device=DEV, dtype=torch.bfloat16)
     nblk = _lib.load().owl_box_final_bwd_blocks(rows)
-    part = torch.zeros(nblk, 5 * D + 4, device=DEV)
+    part = torch.full((nblk, 5 * D + 4), float("nan"), device=DEV)          # scratch: NaN, so a word read before it is written shows
     g = torch.ones(4 * D + 4, device=DEV)                    # dW2 followed by db2, as in the flat bucket; accumulated onto
     cs = torch.ones(D, device=DEV)                           # += column sums of du1 (dense1's bias gradient)
     ops.box_final_bwd(dboxes, sig, h1, u1, w2, du1, part, g, rows, D, du1_colsum=cs)
