@@ -265,6 +265,23 @@ int owl_preprocess_u8_tiles_color(void* stream, const void* desc, const float* c
 /* images that already have the model's size (ABI 6): src u8 [n,H,W,3] (src_chw = 0) or [n,3,H,W] (src_chw = 1) -> lut -> out [n,3,H,W] f32 | bf16.  Pillow's resize
  * to the size an image already has is a copy, so this IS the reference pipeline for such images, bit for bit.  H*W % 4 == 0; src 4-byte, out 16-byte aligned.       */
 int owl_normalize_u8(void* stream, const unsigned char* src, int src_chw, const float* lut, void* out, int out_bf16, int64_t n_images, int64_t H, int64_t W);
+/* OWLv2's input stage (still ABI 8: additive; csrc/pad_resize.hip): HF Owlv2ImageProcessorPil = x(1/255), pad bottom / right to a square of side
+ * S = max(H, W), scipy gaussian_filter(sigma = max(0, (S/N - 1)/2), mode "mirror"), scipy zoom(order 1, "mirror", grid_mode) to N x N, normalise.
+ * owl_pad_resize_coeffs (HOST pointers), one axis of real extent `in_extent` inside a padded axis of length `padded`: row i of (bilinear rows) x (mirrored
+ * Gaussian), formed in f64, restricted to the source indices below in_extent: bounds[2*i] = {first index, tap count} (0 taps: the row lies in the pad),
+ * w[i*ksize + t] the weights rounded once to f32, zero padded to ksize = the largest count (returned; <= 64), wsum[i] = the f64 sum of row i's kept weights
+ * rounded once.  w_capacity in floats (out_size * 64 always suffices).  padded > 16 * out_size is an error.
+ * owl_preprocess_u8_pad_resize (device pointers): one launch pair for a ragged batch.  desc = n_images x 10 int64 in DEVICE memory, the layout of
+ * owl_preprocess_u8_batch's: {src ptr, H, W, bounds_x ptr, w_x ptr, ksize_x, bounds_y ptr, w_y ptr, ksize_y, byte offset of its intermediate in tmp
+ * (a multiple of 16)} with each bounds array followed by ONE more int, `live` = 1 + the last output index with a tap (0: none), and each weight array
+ * (out * ksize floats) followed by its `wsum` (out floats).  Horizontal pass: u8 -> f32 [H, live4_x, 3] in 0..255 units (live4 = live rounded up to 4;
+ * the columns past `live` are written as 0), fmaf in ascending tap order from 0; vertical pass: the same over rows, then -- pad_value != 0 only --
+ * fmaf(pad255, 1 - wsum_x[j] * wsum_y[i], v) with pad255 = fl(255 * pad_value), then fmaf(v, norm[c], norm[3 + c]) (norm: 6 floats in DEVICE memory,
+ * a_c = rescale / std_c and b_c = -mean_c / std_c, each formed in f64 and rounded once) -> out [n_images,3,out_h,out_w] f32 | bf16 (round to nearest
+ * even).  Every element of out is written; tmp needs max over images of offset + H * live4_x * 12 bytes, need not be initialised, and nothing is read
+ * from it that this call did not write.  max_h = the largest H.  tmp_f32 and out 16-byte aligned.                                                    */
+int owl_pad_resize_coeffs(int64_t in_extent, int64_t padded, int64_t out_size, int* bounds, float* w, int64_t w_capacity, int* ksize_out, float* wsum);
+int owl_preprocess_u8_pad_resize(void* stream, const void* desc, int64_t n_images, int64_t max_h, float* tmp_f32, const float* norm, float pad_value, void* out, int out_bf16, int64_t out_h, int64_t out_w);
 
 /* ---- query-bank initialisation: the CLIP-style text tower run once by ref src/models.py:155-169 (HF5:603-663, 945-970).
  * Linear / LayerNorm layers reuse owl_gemm_nt_bf16 / owl_layernorm_fwd; these are the text-only pieces:

@@ -155,6 +155,9 @@ CONFIGS = {
     "owlvit-base-patch32": OwlConfig("owlvit-base-patch32", 768, 32, 768, 12, 3072, 12, 512),
     "owlvit-base-patch16": OwlConfig("owlvit-base-patch16", 768, 16, 768, 12, 3072, 12, 512),
     "owlvit-large-patch14": OwlConfig("owlvit-large-patch14", 840, 14, 1024, 16, 4096, 24, 768),
+    # OWLv2 (google/owlv2-*): the same vision path at 960 / 1008 (native grids 60 / 72); inputs from DeviceImageProcessor(resize="owlv2")
+    "owlv2-base-patch16": OwlConfig("owlv2-base-patch16", 960, 16, 768, 12, 3072, 12, 512),
+    "owlv2-large-patch14": OwlConfig("owlv2-large-patch14", 1008, 14, 1024, 16, 4096, 24, 768),
     # parity-test configs (not real checkpoints)
     "tiny": OwlConfig("tiny", 96, 16, 128, 2, 256, 12, 64, n_classes=4),
     "tiny-l14": OwlConfig("tiny-l14", 96, 16, 128, 2, 256, 14, 64, n_classes=4),
@@ -240,6 +243,8 @@ TEXT_CONFIGS = {
     "owlvit-base-patch32": TextConfig("owlvit-base-text", 512, 8, 2048, 12, 512),
     "owlvit-base-patch16": TextConfig("owlvit-base-text", 512, 8, 2048, 12, 512),
     "owlvit-large-patch14": TextConfig("owlvit-large-text", 768, 12, 3072, 12, 768),
+    "owlv2-base-patch16": TextConfig("owlvit-base-text", 512, 8, 2048, 12, 512),          # Owlv2TextConfig = OwlViTTextConfig, value for value
+    "owlv2-large-patch14": TextConfig("owlvit-large-text", 768, 12, 3072, 12, 768),
     "tiny": TextConfig("tiny-text", 64, 1, 128, 3, 64, vocab=97, max_pos=16),
     "tiny-l14": TextConfig("tiny-text", 64, 1, 128, 3, 64, vocab=97, max_pos=16),
     "small": TextConfig("small-text", 128, 2, 256, 3, 128, vocab=97, max_pos=16),

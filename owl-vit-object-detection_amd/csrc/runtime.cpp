@@ -24,6 +24,7 @@ OWL_API int owl_abi_version(void) { return OWL_ABI_VERSION; }
 // ---------------------------------------------------------------------------------------------------------------------
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 static inline double pil_bicubic(double x) {
     const double a = -0.5;
@@ -91,6 +92,111 @@ OWL_API int owl_bicubic_coeffs_box(int64_t in_size, double in0, double in1, int6
         return -1;
     }
     return bicubic_coeffs_impl("owl_bicubic_coeffs_box", in_size, in0, in1, out_size, bounds, kk, kk_capacity, ksize_out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// OWLv2's input stage (HF Owlv2ImageProcessorPil: pad bottom / right to a square of side S = max(H, W), scipy.ndimage.gaussian_filter with
+// sigma = max(0, (S/N - 1)/2), scipy.ndimage.zoom(order=1, mode="mirror", grid_mode=True) to N x N).  Blur and zoom are separable and linear and the pad
+// is a constant, so per axis the stage is one matrix A = Z G (N x S): the bilinear rows times the mirrored Gaussian.  Row i of A, restricted to the columns
+// below `in_extent` (the real pixels; the others multiply the pad), is what the device kernels (pad_resize.hip) consume.  All in f64, scipy's conventions:
+// lw = int(4 sigma + 0.5), weights exp(-x^2 / (2 sigma^2)) normalised over [-lw, lw] (no blur at all for sigma <= 1e-15), `mirror` (no edge repeat) at
+// the PADDED length for both operators, centre (i + 0.5) S/N - 0.5.
+// ---------------------------------------------------------------------------------------------------------------------
+#define OWL_PAD_RESIZE_MAX_TAPS 64          // per output index and axis: 2 lw + 2 <= 62 at S = 16 N
+
+static inline int64_t mirror_index(int64_t i, int64_t n) {
+    if (n <= 1) return 0;
+    const int64_t period = 2 * (n - 1);
+    i %= period;
+    if (i < 0) i += period;
+    return i < n ? i : period - i;
+}
+
+// bounds[2*i] = {first source index, tap count} of output i (count 0: every tap of the row lies in the pad; leading / trailing zero weights trimmed),
+// w[i*ksize + t] the f64 weights rounded once to f32 (zero padded to ksize = the largest count, at least 1), wsum[i] = the f64 sum of the kept weights
+// rounded once (1 - wsum_x wsum_y is the weight of the pad under an output pixel).  HOST pointers; w_capacity in floats.
+OWL_API int owl_pad_resize_coeffs(int64_t in_extent, int64_t padded, int64_t out_size, int* bounds, float* w, int64_t w_capacity, int* ksize_out, float* wsum) {
+    if (in_extent <= 0 || padded < in_extent || padded > INT32_MAX || out_size <= 0 || !bounds || !w || !ksize_out || !wsum) {
+        owl_set_error("owl_pad_resize_coeffs: bad arguments (extent=%lld padded=%lld out=%lld)", (long long)in_extent, (long long)padded, (long long)out_size);
+        return -1;
+    }
+    if (padded > 16 * out_size) {
+        owl_set_error("owl_pad_resize_coeffs: padded side %lld > 16 x the output side %lld: the blur would need more than %d taps per output pixel",
+                      (long long)padded, (long long)out_size, OWL_PAD_RESIZE_MAX_TAPS);
+        return -1;
+    }
+    const double f = (double)padded / (double)out_size;
+    double sigma = (f - 1.0) / 2.0;
+    if (sigma < 0.0) sigma = 0.0;
+    int lw = 0;
+    double g[2 * 32 + 1];
+    g[0] = 1.0;
+    if (sigma > 1e-15) {
+        lw = (int)(4.0 * sigma + 0.5);
+        if (lw > 32) { owl_set_error("owl_pad_resize_coeffs: blur radius %d too large", lw); return -1; }
+        double sum = 0.0;
+        for (int k = -lw; k <= lw; k++) { g[k + lw] = exp(-0.5 / (sigma * sigma) * (double)(k * k)); sum += g[k + lw]; }
+        for (int k = 0; k <= 2 * lw; k++) g[k] /= sum;
+    }
+    // pass 1: the rows into a scratch of OWL_PAD_RESIZE_MAX_TAPS per output (ksize is known only afterwards)
+    double* rows = (double*)malloc(sizeof(double) * (size_t)out_size * OWL_PAD_RESIZE_MAX_TAPS);
+    if (!rows) { owl_set_error("owl_pad_resize_coeffs: out of memory"); return -1; }
+    int ksize = 1, rc = 0;
+    for (int64_t i = 0; i < out_size && rc == 0; i++) {
+        const double cc = ((double)i + 0.5) * f - 0.5;
+        const double fl = floor(cc), t = cc - fl;
+        const int64_t z0 = (int64_t)fl;
+        const double zw[2] = {1.0 - t, t};
+        int64_t idx[2 * 65];
+        double val[2 * 65];
+        int n = 0;
+        int64_t lo = INT64_MAX, hi = -1;
+        for (int a = 0; a < 2; a++) {
+            if (zw[a] == 0.0) continue;
+            const int64_t zi = mirror_index(z0 + a, padded);
+            for (int k = -lw; k <= lw; k++) {
+                idx[n] = mirror_index(zi + k, padded);
+                val[n] = zw[a] * g[k + lw];
+                if (idx[n] < lo) lo = idx[n];
+                if (idx[n] > hi) hi = idx[n];
+                n++;
+            }
+        }
+        if (hi >= in_extent) hi = in_extent - 1;                  // indices in the pad drop out
+        double* row = rows + i * OWL_PAD_RESIZE_MAX_TAPS;
+        int count = 0;
+        if (lo <= hi) {
+            if (hi - lo + 1 > OWL_PAD_RESIZE_MAX_TAPS) { owl_set_error("owl_pad_resize_coeffs: output %lld spans %lld source pixels", (long long)i, (long long)(hi - lo + 1)); rc = -1; break; }
+            count = (int)(hi - lo + 1);
+            for (int q = 0; q < count; q++) row[q] = 0.0;
+            for (int q = 0; q < n; q++)                            // reflected taps add onto their index, in tap order
+                if (idx[q] <= hi) row[idx[q] - lo] += val[q];
+            int head = 0;
+            while (head < count && row[head] == 0.0) head++;
+            while (count > head && row[count - 1] == 0.0) count--;
+            count -= head;
+            for (int q = 0; q < count; q++) row[q] = row[q + head];
+            lo += head;
+        }
+        double s = 0.0;
+        for (int q = 0; q < count; q++) s += row[q];
+        wsum[i] = (float)s;
+        bounds[2 * i] = count ? (int)lo : 0;
+        bounds[2 * i + 1] = count;
+        if (count > ksize) ksize = count;
+    }
+    if (rc == 0 && (int64_t)ksize * out_size > w_capacity) {
+        owl_set_error("owl_pad_resize_coeffs: w capacity %lld < %lld", (long long)w_capacity, (long long)ksize * out_size);
+        rc = -1;
+    }
+    if (rc == 0) {
+        for (int64_t i = 0; i < out_size; i++)
+            for (int q = 0; q < ksize; q++)
+                w[i * ksize + q] = q < bounds[2 * i + 1] ? (float)rows[i * OWL_PAD_RESIZE_MAX_TAPS + q] : 0.0f;
+        *ksize_out = ksize;
+    }
+    free(rows);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

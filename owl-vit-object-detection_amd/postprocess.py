@@ -29,6 +29,24 @@ import torch
 from . import ops
 
 
+def unpad_boxes(boxes, sizes, to="pixels"):
+    """Boxes predicted on a `DeviceImageProcessor(resize="owlv2")` input are normalised to the PADDED square of side S = max(h, w), the image at its top
+    left.  boxes [B, n, 4] (xyxy) with `sizes` [B, 2] = the images' (height, width) -- a tensor or a list of pairs -- or boxes [n, 4] with one pair.
+    to="pixels": HF's Owlv2 `_scale_boxes`, both axes times S -> pixel coordinates of the original image (`boxes * S`, the same multiply).
+    to="normalized": x * S / w, y * S / h -> normalised to the image itself, the frame of the reference's targets (formed in float64, rounded once);
+    the inverse of preprocess.pad_square_targets.  Torch ops on the boxes' device, no sync."""
+    if to not in ("pixels", "normalized"):
+        raise ValueError(f"unpad_boxes: to={to!r}: \"pixels\" or \"normalized\"")
+    sizes = torch.as_tensor(sizes, device=boxes.device)
+    h, w = sizes[..., 0], sizes[..., 1]
+    s = torch.maximum(h, w)
+    if to == "pixels":
+        return boxes * torch.stack([s, s, s, s], dim=-1).unsqueeze(-2)
+    h, w, s = h.double(), w.double(), s.double()
+    fx, fy = s / w, s / h
+    return (boxes.double() * torch.stack([fx, fy, fx, fy], dim=-1).unsqueeze(-2)).to(boxes.dtype)
+
+
 class PostProcess:
     def __init__(self, confidence_threshold=0.75, iou_threshold=0.3, *, nms_route="torchvision_gpu"):   # ref models.py:123-125 (same defaults)
         if nms_route not in ops.NMS_ROUTES:

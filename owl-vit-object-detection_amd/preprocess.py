@@ -9,6 +9,13 @@ normalisation is a 768-entry table of the reference's own float results.  Output
 contract) or bf16 (what the patch-embed loader consumes) on the device.  No CPU fallback: the resize runs in
 libowlhip.so or not at all; only Pillow's f64 tap tables are computed on the host (``owl_bicubic_coeffs``), cached
 per image size.
+
+``DeviceImageProcessor(size, resize="owlv2")`` is HF's ``Owlv2ImageProcessorPil`` instead (what the ``google/owlv2-*`` checkpoints were trained behind):
+x(1/255), pad bottom / right to a square of side S = max(H, W), scipy's Gaussian blur with sigma = max(0, (S/N - 1)/2) and bilinear zoom to N x N (both
+"mirror"), normalise.  Blur and zoom are separable and linear and the pad is a constant, so the stage folds into one float tap table per axis
+(``owl_pad_resize_coeffs``, host, f64) and the same two passes with float weights and an f32 intermediate (csrc/pad_resize.hip).  Not bit-exact -- HF
+itself stores f32 between scipy's passes -- but inside a bound that counts every rounding (tests/owlv2_input_reference.py).  Predictions on such an input
+are normalised to the PADDED square: ``postprocess.unpad_boxes`` maps them back, ``pad_square_targets`` maps training targets in.
 """
 import math
 
@@ -46,18 +53,38 @@ def _size_attr(size):
     return H if H == W else (H, W)
 
 
+PAD_RESIZE_MAX_RATIO = 16   # owl_pad_resize_coeffs: padded side S <= 16 x the model size N (the blur then has at most 62 taps per axis)
+_PAD_TAPS = 64              # capacity per output index handed to owl_pad_resize_coeffs
+
+_OWLV2_PLAIN_ONLY = ("{what} is not built for resize=\"owlv2\": crop, flip, mosaic, colour jitter and slices resample with Pillow's bicubic into a "
+                     "canvas without a pad, which is not the input an OWLv2 checkpoint expects.  The plain path -- __call__, normalize_sized, "
+                     "DevicePrefetcher(processor=) without augment= -- runs in this mode")
+
 _SQUARE_ONLY = ("{what} takes a square size: crop / flip / mosaic canvases, colour jitter and slices are built for S x S model inputs and the size "
                 "here is {size} (height, width).  The plain path -- __call__, normalize_sized, DevicePrefetcher without augment= -- runs at a rectangular size")
 
 
 class DeviceImageProcessor:
     """`size`: the model's input size, an int (square) or a pair (height, width).  The plain path (__call__: Pillow's resize of each image to H x W plus the
-    table; normalize_sized) runs at either; the tile paths (run_tiles / tiles / slices) are square only and raise ValueError on a rectangle."""
+    table; normalize_sized) runs at either; the tile paths (run_tiles / tiles / slices) are square only and raise ValueError on a rectangle.
+
+    `resize`: "pillow" (the default: HF's OwlViTImageProcessor, every launch and bit as ever) or "owlv2" (HF's Owlv2ImageProcessorPil: pad bottom / right
+    to a square, blur, bilinear zoom -- the module docstring).  In "owlv2" mode `size` must be square (the pad makes a square), an image's longer side may be
+    at most PAD_RESIZE_MAX_RATIO x size, and only the plain path runs: run_tiles / tiles / slices raise ValueError.  `pad_value`: the level of the pad in
+    pre-normalisation [0, 1] units (a fraction of the u8 range).  HF pads 0.0; other OWLv2 pipelines pad mid-grey, 0.5."""
 
     def __init__(self, size=768, image_mean=CLIP_MEAN, image_std=CLIP_STD, rescale_factor=1 / 255, device="cuda",
-                 dtype=torch.float32):
+                 dtype=torch.float32, resize="pillow", pad_value=0.0):
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("DeviceImageProcessor: dtype must be torch.float32 or torch.bfloat16")
+        if resize not in ("pillow", "owlv2"):
+            raise ValueError(f"DeviceImageProcessor: resize={resize!r}: \"pillow\" or \"owlv2\"")
+        if resize == "owlv2" and len(set(size_hw(size))) > 1:
+            raise ValueError(f"DeviceImageProcessor: resize=\"owlv2\" pads every image to a square and takes a square size; got {tuple(size_hw(size))} (height, width)")
+        if not 0.0 <= float(pad_value) <= 1.0:
+            raise ValueError(f"DeviceImageProcessor: pad_value={pad_value!r} is in pre-normalisation units: 0 <= pad_value <= 1")
+        self.resize = resize
+        self.pad_value = float(pad_value)
         self.size = _size_attr(size)         # the int for a square, (H, W) for a rectangle
         self.hw = size_hw(size)
         self.device = torch.device(device)
@@ -66,8 +93,15 @@ class DeviceImageProcessor:
         self._tables = {}
         self._tmp = None
         self._ws = None                      # partial sums of the colour path (owl_preprocess_color_workspace_bytes)
+        # resize="owlv2": one affine step per channel, a_c = rescale / std_c and b_c = -mean_c / std_c, each formed in f64 and rounded once
+        m, sd = np.asarray(image_mean, dtype=np.float64), np.asarray(image_std, dtype=np.float64)
+        self._norm = torch.from_numpy(np.concatenate([rescale_factor / sd, -m / sd]).astype(np.float32)).to(self.device) if resize == "owlv2" else None
+        self._pad_tables = {}
+        self._tmp_f32 = None
 
     def _square(self, what: str):
+        if self.resize == "owlv2":
+            raise ValueError(_OWLV2_PLAIN_ONLY.format(what=what))
         if isinstance(self.size, tuple):
             raise ValueError(_SQUARE_ONLY.format(what=what, size=self.size))
 
@@ -83,6 +117,57 @@ class DeviceImageProcessor:
             self._tables[key] = (bounds.to(self.device), kk.to(self.device), ksize)
         return self._tables[key]
 
+    def _pad_axis_tables(self, extent: int, padded: int, out: int):
+        """resize="owlv2": the float tap table of one axis of `extent` real pixels inside the padded length -> (bounds int32 [2 out + 1] = {first, count}
+        per output then `live`, weights f32 [out ksize + out] = the rows then their sums, ksize, live4), cached on the device."""
+        key = (extent, padded, out)
+        if key not in self._pad_tables:
+            bounds = torch.zeros(out * 2 + 1, dtype=torch.int32)
+            w = torch.zeros(out * _PAD_TAPS, dtype=torch.float32)
+            wsum = torch.zeros(out, dtype=torch.float32)
+            ks = torch.zeros(1, dtype=torch.int32)
+            _lib.call("owl_pad_resize_coeffs", extent, padded, out, bounds, w, w.numel(), ks, wsum)
+            ksize = int(ks.item())
+            has = torch.nonzero(bounds[1:2 * out:2]).reshape(-1)
+            live = int(has[-1]) + 1 if has.numel() else 0
+            bounds[2 * out] = live
+            self._pad_tables[key] = (bounds.to(self.device), torch.cat([w[:out * ksize], wsum]).to(self.device), ksize, (live + 3) // 4 * 4)
+        return self._pad_tables[key]
+
+    def _pad_resize_plan(self, imgs):
+        """resize="owlv2": the host half of one launch -> (descriptor rows: 10 ints per image, as owl_preprocess_u8_pad_resize reads them; bytes of the
+        f32 intermediate; the largest image height).  Raises ValueError, before any table is built, if an image exceeds PAD_RESIZE_MAX_RATIO."""
+        N = self.hw[0]
+        for im in imgs:
+            S = max(int(im.shape[0]), int(im.shape[1]))
+            if S > PAD_RESIZE_MAX_RATIO * N:
+                raise ValueError(f"DeviceImageProcessor(resize=\"owlv2\"): an image of {int(im.shape[0])} x {int(im.shape[1])} pads to a square of side {S}, more than "
+                                 f"{PAD_RESIZE_MAX_RATIO} x the model size {N} = {PAD_RESIZE_MAX_RATIO * N}: the blur would need more than {_PAD_TAPS} taps per "
+                                 "pixel and axis.  Downscale such an image first")
+        rows, off, max_h = [], 0, 0
+        for im in imgs:
+            H, W = int(im.shape[0]), int(im.shape[1])
+            S = max(H, W)
+            bx, wx, ksx, live4 = self._pad_axis_tables(W, S, N)
+            by, wy, ksy, _ = self._pad_axis_tables(H, S, N)
+            rows.append((im.data_ptr(), H, W, bx.data_ptr(), wx.data_ptr(), ksx, by.data_ptr(), wy.data_ptr(), ksy, off))
+            off += (H * live4 * 12 + 255) // 256 * 256           # the horizontal pass's f32 intermediate: H rows of live4 pixels
+            max_h = max(max_h, H)
+        return rows, off, max_h
+
+    def _call_owlv2(self, imgs):
+        """One launch pair for the (ragged) batch: owl_preprocess_u8_pad_resize."""
+        n, N = len(imgs), self.hw[0]
+        rows, tmp_bytes, max_h = self._pad_resize_plan(imgs)     # (raises before anything is allocated or launched)
+        out = torch.empty(n, 3, N, N, dtype=self.dtype, device=self.device)
+        if self._tmp_f32 is None or self._tmp_f32.numel() * 4 < tmp_bytes:
+            self._tmp_f32 = torch.empty(tmp_bytes // 4, dtype=torch.float32, device=self.device)
+        desc_d = torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(self.device, non_blocking=True)
+        _lib.call("owl_preprocess_u8_pad_resize", ops.stream(), desc_d, n, max_h, self._tmp_f32, self._norm, self.pad_value, out,
+                  1 if self.dtype == torch.bfloat16 else 0, N, N)
+        self._keep = (imgs, desc_d)          # keep the sources alive until the stream has consumed them
+        return {"pixel_values": out}
+
     def _to_device(self, img):
         if isinstance(img, np.ndarray):
             img = torch.from_numpy(np.ascontiguousarray(img))
@@ -95,6 +180,8 @@ class DeviceImageProcessor:
     def __call__(self, images, return_tensors="pt", **_):
         single = not isinstance(images, (list, tuple))
         imgs = [self._to_device(im) for im in ([images] if single else list(images))]
+        if self.resize == "owlv2":
+            return self._call_owlv2(imgs)
         n = len(imgs)
         out_h, out_w = self.hw
         out = torch.empty(n, 3, out_h, out_w, dtype=self.dtype, device=self.device)
@@ -180,6 +267,19 @@ class DeviceImageProcessor:
         out = torch.empty(n, 3, H, W_, dtype=self.dtype, device=self.device)
         _lib.call("owl_normalize_u8", ops.stream(), src_u8, 1 if chw else 0, self.lut, out, 1 if self.dtype == torch.bfloat16 else 0, n, H, W_)
         return out
+
+
+def pad_square_targets(boxes_xyxy_norm, sizes):
+    """Training targets for a resize="owlv2" input: normalised xyxy boxes in the frame of the IMAGE -> the frame of the padded square the model sees
+    (x * W / S, y * H / S with S = max(H, W); the image sits at the top left, so nothing shifts).  boxes [..., n, 4] with `sizes` [..., 2] = (height, width)
+    per leading index, or boxes [n, 4] with one (height, width).  Torch ops on the boxes' device, no sync; the inverse of
+    postprocess.unpad_boxes(to="normalized")."""
+    sizes = torch.as_tensor(sizes, device=boxes_xyxy_norm.device).double()
+    h, w = sizes[..., 0], sizes[..., 1]
+    s = torch.maximum(h, w)
+    fx, fy = w / s, h / s
+    # (formed in float64 and rounded once, so that unpad_boxes(to="normalized") of the result is the input to 1 ulp)
+    return (boxes_xyxy_norm.double() * torch.stack([fx, fy, fx, fy], dim=-1).unsqueeze(-2)).to(boxes_xyxy_norm.dtype)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -710,6 +810,8 @@ class DevicePrefetcher:
         self.augment = augment
         if augment is not None and isinstance(self.size, tuple):
             raise ValueError(_SQUARE_ONLY.format(what="DevicePrefetcher(augment=)", size=self.size))
+        if augment is not None and getattr(self.processor, "resize", "pillow") == "owlv2":
+            raise ValueError(_OWLV2_PLAIN_ONLY.format(what="DevicePrefetcher(augment=)"))
         if augment is not None and augment.size != self.size:
             raise ValueError(f"DevicePrefetcher: augment.size = {augment.size} but size = {self.size}")
         self.augment_seconds = 0.0         # of which: drawing the tiles and building their tap tables and descriptors

@@ -27,8 +27,8 @@ class TextTower:
         src = state if state is not None else W_.make_text_weights(tcfg, seed)
         g = {}
         for name, shape in W_.text_param_shapes(tcfg).items():
-            key = name if name in src else "owlvit." + name
-            if key not in src:
+            key = next((k for k in (name, "owlvit." + name, "owlv2." + name) if k in src), None)          # bare, OwlViT or Owlv2 state dict names
+            if key is None:
                 raise KeyError(f"TextTower: missing parameter {name}")
             t = torch.as_tensor(src[key]).detach().to(torch.float32).reshape(shape).contiguous()
             g[name] = t.to(self.device)

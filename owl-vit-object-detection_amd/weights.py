@@ -260,7 +260,11 @@ def from_hf_state_dict(sd, queries=None) -> "OrderedDict[str, np.ndarray]":
     `owlvit.vision_model`, `post_post_layernorm` = HF `layer_norm`, `class_predictor` = HF `class_head`, `box_head` unchanged).  Only the tensors
     the vision path owns are taken (the text tower stays with `text.TextTower`; `class_head.logit_shift / logit_scale` are dropped by the reference,
     src/models.py:24-38).  `queries` ([1, 3C, Dt] or [3C, Dt]) is the reference's `query_bank` (src/models.py:161-169); pass it here or add it to
-    the result before `load_model(..., state=)`.  Values may be torch tensors or arrays; the result holds float32 ndarrays."""
+    the result before `load_model(..., state=)`.  Values may be torch tensors or arrays; the result holds float32 ndarrays.
+
+    An `Owlv2ForObjectDetection.state_dict()` is the same dict under the prefix `owlv2.` in place of `owlvit.` (the vision tower, the encoder layers and
+    both heads are source-identical after renaming), plus six `objectness_head.*` tensors.  Both prefixes are taken; `objectness_head.*` is skipped like
+    the other tensors this path does not own (the objectness head is not built).  Such a checkpoint expects `DeviceImageProcessor(resize="owlv2")`."""
     out = OrderedDict()
 
     def arr(v):
@@ -270,6 +274,8 @@ def from_hf_state_dict(sd, queries=None) -> "OrderedDict[str, np.ndarray]":
     for k, v in sd.items():
         if k.startswith("owlvit.vision_model."):
             name = "backbone." + k[len("owlvit.vision_model."):]
+        elif k.startswith("owlv2.vision_model."):                # Owlv2ForObjectDetection: the same tensors under another prefix
+            name = "backbone." + k[len("owlv2.vision_model."):]
         elif k.startswith("vision_model."):                      # a bare OwlViTModel / vision tower state dict
             name = "backbone." + k[len("vision_model."):]
         elif k.startswith("layer_norm."):
@@ -279,7 +285,7 @@ def from_hf_state_dict(sd, queries=None) -> "OrderedDict[str, np.ndarray]":
         elif k.startswith("box_head."):
             name = k
         else:
-            continue                                             # text tower, projections, logit shift / scale, buffers
+            continue                                             # text tower, projections, logit shift / scale, objectness_head.* (OWLv2), buffers
         if name.endswith("position_ids"):
             continue
         out[name] = arr(v)
@@ -293,7 +299,8 @@ LOGIT_HEAD_KEYS = ("logit_shift.weight", "logit_shift.bias", "logit_scale.weight
 
 
 def hf_logit_head(sd) -> "OrderedDict[str, np.ndarray]":
-    """The four tensors of HF's `class_head.logit_shift / logit_scale` (two Linear(D, 1)) out of an `OwlViTForObjectDetection.state_dict()`, which
+    """The four tensors of HF's `class_head.logit_shift / logit_scale` (two Linear(D, 1)) out of an `OwlViTForObjectDetection.state_dict()` (or an
+    `Owlv2ForObjectDetection` one: the class head sits outside the `owlvit.` / `owlv2.` prefix and has the same names), which
     `from_hf_state_dict` drops as the reference does: {"logit_shift.weight" [D], "logit_shift.bias" [], "logit_scale.weight" [D], "logit_scale.bias" []},
     float32 ndarrays.  They are NOT parameters of the model (param_shapes, the flat bucket and every state dict stay as they are): hand them to
     `OwlViT.set_logit_head` / `load_model(..., logit_head=)` for zero-shot inference (`detect`).  Values may be torch tensors or arrays; a missing tensor
@@ -352,7 +359,7 @@ def count_trainable(cfg: OwlConfig, keep=FREEZE_KEEP) -> int:
 
 # ---- text tower (query-bank initialisation, ref src/models.py:155-169) ------------------------------------------------
 def text_param_shapes(tc) -> "OrderedDict[str, tuple]":
-    """HF names below ``owlvit.`` (``text_model.*``, ``text_projection.weight``)."""
+    """HF names below ``owlvit.`` -- or ``owlv2.`` -- (``text_model.*``, ``text_projection.weight``)."""
     W, I = tc.width, tc.mlp
     s = OrderedDict()
     s["text_model.embeddings.token_embedding.weight"] = (tc.vocab, W)
