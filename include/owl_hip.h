@@ -333,6 +333,15 @@ int owl_query_normalize_wide_bwd(void* stream, const float* dqhat_wide, const fl
  * du1_colsum (optional, [D]): += column sums of du1 = dense1's bias gradient, from the same pass */
 int owl_box_final_bwd_blocks(int64_t rows);
 int owl_box_final_bwd(void* stream, const float* dboxes, const float* sig, const void* h1_bf16, const void* u1_bf16, const float* w2, void* du1_bf16, float* partials, float* dw2_db2, int64_t rows, int64_t D, float* du1_colsum);
+/* OWLv2's objectness head, its tail (csrc/objectness.hip; still ABI 8: additive).  HF: Owlv2BoxPredictionHead(out_dim=1) on the detached image features; the two
+ * hidden layers are owl_gemm_nt_bf16 launches (epi 2 forward; epi 9 and the weight-gradient route backward).  D % 8 == 0, 8 <= D <= 1024, rows >= 1.
+ * fwd: logits[r] = sum_j h[r, j] w2[j] + b2   (h bf16 [rows, D], w2 f32 [D], b2 f32 [1], logits f32 [rows]).
+ * bwd: du1 = bf16(g_r w2_j gelu'(u1_rj)) (erf form), dw2_j = sum_r g_r h1_rj, db2 = sum_r g_r, du1_colsum_j = sum_r du1_rj (f32, before the bf16 rounding: dense1's
+ *   bias gradient; optional).  dw2_db2: f32 [D + 4] = dw2 [D], db2, three zeros (the reducer works in quads).  partials: f32
+ *   [owl_objectness_final_bwd_blocks(rows)][2 D + 4] scratch.  Every output is WRITTEN, not accumulated into; no atomics, fixed summation order. */
+int owl_objectness_final_fwd(void* stream, const void* h_bf16, const float* w2, const float* b2, float* logits, int64_t rows, int64_t D);
+int owl_objectness_final_bwd_blocks(int64_t rows);
+int owl_objectness_final_bwd(void* stream, const float* dlogits, const void* h1_bf16, const void* u1_bf16, const float* w2, void* du1_bf16, float* partials, float* dw2_db2, int64_t rows, int64_t D, float* du1_colsum);
 /* The box head's two dX GEMMs on the rows that carry a gradient (csrc/box_rows_bwd.hip; still ABI 8: additive).  The box losses read pred_boxes at the
  * matched predictions only (ref src/losses.py `src_boxes = outputs["pred_boxes"][idx]`), so dboxes f32 [rows, 4] is zero in all but at most `cap` rows, a
  * bound the host knows without a sync.  Every kernel takes the row count from device memory; the grids are sized from cap / cap_pad (a multiple of 8, >= cap).

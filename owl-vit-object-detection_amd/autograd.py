@@ -143,6 +143,64 @@ class OwlViTQueryFunction(torch.autograd.Function):
         return (None, None, dq, None) + (None,) * nflat + hg
 
 
+class OwlViTObjectnessFunction(torch.autograd.Function):
+    """OWLv2's objectness head with a TRAINABLE head (models.OwlViT.set_objectness_head(head, trainable=True)), called by forward_queries(..., objectness=True)
+    right behind the recording forward: o = dense2(gelu(dense1(gelu(dense0(feats))))) on the training workspace's feats, read as a constant (HF detaches
+    them: there is no dX into the trunk).  Inputs: the six leaves in weights.OBJECTNESS_HEAD_KEYS' order.  backward returns views of ONE flat f32 gradient
+    (the layout of the head's parameter buffer), written, not accumulated into.  It shares no scratch with backward_impl -- activations, du1 / du0, the
+    tail's partials, the transposed weight and the weight-gradient scratch are its own (_objectness_bws) -- and runs on the caller's stream, so it may
+    run before, after or without the main backward, in line or beside the deferred tail, with the same bits; model.flat_grad is not touched."""
+
+    @staticmethod
+    def forward(ctx, model, B, *leaves):
+        out = model._objectness_train_forward(B)
+        ctx.model, ctx.B = model, B
+        ctx.gen = model._workspace(B)["gen"]
+        return out
+
+    @staticmethod
+    def backward(ctx, d_obj):
+        model, B = ctx.model, ctx.B
+        if model._workspace(B)["gen"] != ctx.gen or ("obj", B) not in model._ws:
+            raise RuntimeError(
+                f"OwlViT backward: the activations of this forward (batch size {B}) were overwritten by a later gradient-recording "
+                "forward at the same batch size (or evicted: only the model's `max_cached_batch_sizes` most recent batch sizes keep their "
+                "workspaces); call backward() before the next training forward (no-grad / eval forwards are fine)")
+        if not any(ctx.needs_input_grad[2:]):
+            return (None,) * 8
+        cfg = model.cfg
+        D, Mh = cfg.hidden, B * cfg.patches
+        ws, ow, bw = model._workspace(B), model._objectness_ws(B), _objectness_bws(model, B)
+        oh, at = model.objectness_head, model._objectness_layout()[0]
+        g = torch.zeros(model._objectness_layout()[1], dtype=torch.float32, device=d_obj.device)          # (dense0's bias gradient is added into: it starts at zero)
+        view = lambda k: g[at[k][0]:at[k][1]].view(at[k][2])
+        d = d_obj.contiguous().float().view(-1)
+        a2 = at["dense2.weight"][0]
+        ops.objectness_final_bwd(d, ow["h1"], ow["u1"], oh["dense2.weight"].detach(), bw["du1"], bw["part"], g[a2:a2 + D + 4], Mh, D,
+                                 du1_colsum=view("dense1.bias"))
+        weight_grad(bw["du1"], ow["h0"], view("dense1.weight"), D, D, Mh, bw["dw"], accumulate=0)
+        ops.transpose_bf16(model._objectness_bf16["dense1.weight"], bw["w1T"], D, D)
+        ops.gemm(ops.EPI_DGELU_BF16, bw["du1"], bw["w1T"], bw["du0"], aux=ow["u0"], M=Mh, N=D, K=D)
+        weight_grad(bw["du0"], ws["feats"], view("dense0.weight"), D, D, Mh, bw["dw"], view("dense0.bias"), accumulate=0)
+        from . import weights as W
+        return (None, None) + tuple(view(k) for k in W.OBJECTNESS_HEAD_KEYS)
+
+
+def _objectness_bws(model, B):
+    """Backward scratch of the objectness head at this batch size, allocated when its first backward runs: du1 / du0 bf16 [B P, D], the tail's partials, the
+    bf16 transpose of dense1.weight and a weight_grad scratch of its own (nothing of _bws(): the main backward may be running beside this one)."""
+    key = ("obj_bwd", B)
+    if key in model._ws:
+        return model._ws[key]
+    D, Mh, dev = model.cfg.hidden, B * model.cfg.patches, model.device_
+    bf, z = torch.bfloat16, ops.zeros_rows
+    dw = dw_scratch(D, D, Mh, dev, bias=True)          # (both products are D x D; dense0's carries the bias gradient)
+    bw = dict(du1=z(Mh, D, bf, dev), du0=z(Mh, D, bf, dev), part=torch.zeros(ops.objectness_final_bwd_blocks(Mh), 2 * D + 4, device=dev),
+              w1T=torch.zeros(D, D, dtype=bf, device=dev), dw=dw)
+    model._ws[key] = bw
+    return bw
+
+
 def _bws(model, B):
     key = ("bwd", B)
     if key in model._ws:
@@ -342,13 +400,23 @@ def weight_grad(dy, x, grad_w, n_out, n_in, rows, scratch, grad_b=None, accumula
         _lib.call("owl_slab_reduce_rows", ops.stream(), slab, grad_w, n_out, n_in, Kp, n_out * Kp, ns, accumulate)
 
 
+def dw_scratch(n_out, n_in, rows, device, bias=False):
+    """A weight_grad() scratch of its own for one product shape at `rows` rows, for callers outside backward_impl's three lanes: the split-K slab, the
+    NT route's transposed-operand pair where _dw_plan() takes that route and, with a bias gradient, the per-split bias slab (256 splits at most) and the
+    column reduction's partials."""
+    plan, ld, bf = _dw_plan(n_out, n_in, bias=bias), ops.pad_rows(rows), torch.bfloat16
+    scratch = dict(slab=torch.zeros(plan.slab_elems, device=device), tn_all=False,
+                   tA=None if plan.tn else torch.zeros(n_out, ld, dtype=bf, device=device), tB=None if plan.tn else torch.zeros(n_in, ld, dtype=bf, device=device))
+    if bias:
+        scratch.update(bslab=torch.zeros(256 * n_out, device=device), part=torch.zeros(ops.part_floats(rows, n_out), device=device))
+    return scratch
+
+
 def patch_weight_grad(dE, patches, grad_w, D, K, rows, scratch=None, accumulate=1):
     """grad_w [D, K] (+)= dE[rows, D]^T patches[rows, K] -- the patch-embedding weight gradient: weight_grad() without a bias (scratch as there; default:
     allocated here)."""
     if scratch is None:
-        plan, ld, dev = _dw_plan(D, K), ops.pad_rows(rows), dE.device
-        scratch = dict(slab=torch.zeros(plan.slab_elems, device=dev),
-                       tA=None if plan.tn else torch.zeros(D, ld, dtype=torch.bfloat16, device=dev), tB=None if plan.tn else torch.zeros(K, ld, dtype=torch.bfloat16, device=dev))
+        scratch = dw_scratch(D, K, rows, dE.device)
     weight_grad(dE, patches, grad_w, D, K, rows, scratch, accumulate=accumulate)
 
 

@@ -34,8 +34,9 @@ for f in $SRCS; do
       #  tests/logit_head_grad_reference.py counts on exact f64 products and separately rounded f64 adds in the head-gradient sums)
       # (open_vocab_loss.hip: tests/open_vocab_loss_reference.py counts one rounding per written operation of the cost, the focal term and the box pairs)
       # (pad_resize.hip: its two fmaf chains, pad term and affine step are the sequence tests/owlv2_input_reference.py bounds rounding by rounding)
+      # (objectness.hip: tests/objectness_reference.py counts one rounding per written operation of the two tail kernels; their fused steps are named fmaf)
       # (box_rows_bwd.hip is NOT in this list: its tail is held bit for bit to backward.hip's box_final_bwd_kernel, so it takes backward.hip's flags)
-      loss.hip|postprocess.hip|metrics.hip|pos_resample.hip|image_query.hip|open_vocab.hip|open_vocab_bwd.hip|open_vocab_loss.hip|color_jitter.hip|slice_merge.hip|pad_resize.hip) extra="-ffp-contract=off";;
+      loss.hip|postprocess.hip|metrics.hip|pos_resample.hip|image_query.hip|open_vocab.hip|open_vocab_bwd.hip|open_vocab_loss.hip|color_jitter.hip|slice_merge.hip|pad_resize.hip|objectness.hip) extra="-ffp-contract=off";;
       # packed f32 VALU (v_pk_mul/add_f32) beside MFMAs costs more than the two scalar instructions it replaces
       # (MI355X_MICROARCH.md; measured -1.7 % on the backward pair): no SLP packing in the attention kernels
       attention_bwd.hip|attention_fwd.hip) extra="-fno-slp-vectorize";;

@@ -251,6 +251,10 @@ class OwlViT(nn.Module):
         # every state dict (plain attributes, as box_bias is); None until set_logit_head
         self.logit_head = None
         self._logit_head_flat = None          # the one buffer behind a TRAINABLE head's four leaf views (set_logit_head(head, trainable=True))
+        # OWLv2's objectness head (HF `objectness_head.*`), on the same terms: None until set_objectness_head
+        self.objectness_head = None
+        self._objectness_flat = None          # the one buffer behind a TRAINABLE head's six leaf views
+        self._objectness_bf16 = None          # bf16 copies of dense0.weight / dense1.weight for the GEMMs
 
     # -- module-tree plumbing -----------------------------------------------------------------------
     def _attach(self, dotted: str, p: nn.Parameter):
@@ -1002,8 +1006,110 @@ class OwlViT(nn.Module):
             out[k] = np.ascontiguousarray(v.reshape(-1)) if k.endswith("weight") else v.reshape(()).copy()
         return out
 
+    # -- OWLv2's objectness head: HF's `objectness_predictor` on the detached image features -------------------------------------
+    def _objectness_layout(self):
+        """Where the six tensors sit in the head's flat f32 buffer (parameters and gradient alike): dense0.weight | dense0.bias | dense1.weight | dense1.bias |
+        dense2.weight | dense2.bias | three pad zeros (the tail's reducer writes dw2, db2 in quads) -> ({key: (begin, end, shape)}, elements)."""
+        D = self.cfg.hidden
+        at, o = {}, 0
+        for k, shape in zip(W.OBJECTNESS_HEAD_KEYS, ((D, D), (D,), (D, D), (D,), (D,), (1,))):
+            n = int(np.prod(shape))
+            at[k] = (o, o + n, shape)
+            o += n
+        return at, o + 3
+
+    def set_objectness_head(self, head, trainable=False):
+        """head: weights.hf_objectness_head(sd) -- {"dense0.weight" [D, D], "dense0.bias" [D], "dense1.weight" [D, D], "dense1.bias" [D], "dense2.weight" [D],
+        "dense2.bias" []} (arrays or tensors; HF's [1, D] / [1] shapes of dense2 are taken too).  They become frozen f32 device buffers in
+        `model.objectness_head` plus bf16 copies of the two D x D weights for the GEMMs, outside flat_param, parameters() and state_dict().  None removes
+        them.  ValueError names a tensor of the wrong size, KeyError a missing one.
+
+        trainable=True: the six tensors live in ONE flat f32 device buffer (_objectness_layout) and `model.objectness_head` holds six leaf views of it with
+        requires_grad=True; the bf16 copies are re-cast behind every forward that reads them.  `forward_queries(..., objectness=True)` then gives them
+        ordinary autograd gradients (autograd.OwlViTObjectnessFunction).  They are still NOT registered parameters: parameters(), state_dict(), flat_param /
+        flat_grad, FusedAdamW, its EMA and ddp.DataParallel see nothing new, and no `trainable=` substring reaches them.  The caller steps them with a torch
+        optimizer over `model.objectness_head_parameters()` (and all-reduces their gradients under data parallel) and writes them back to HF through
+        `model.objectness_head_state()`.  The head reads the features DETACHED, as HF does: no gradient of it reaches the trunk."""
+        if head is None:
+            self.objectness_head = self._objectness_flat = self._objectness_bf16 = None
+            return self
+        at, n = self._objectness_layout()
+        flat = torch.zeros(n, dtype=torch.float32)
+        for k in W.OBJECTNESS_HEAD_KEYS:
+            if k not in head:
+                raise KeyError(f"set_objectness_head: `{k}` is missing (weights.hf_objectness_head builds the six tensors)")
+            t = torch.as_tensor(np.asarray(head[k].detach().cpu() if torch.is_tensor(head[k]) else head[k]), dtype=torch.float32)
+            a, b, shape = at[k]
+            ok = t.numel() == b - a and (tuple(t.shape) == shape or k.startswith("dense2"))
+            if not ok:
+                raise ValueError(f"set_objectness_head: `{k}` must be {list(shape)} for hidden size {self.cfg.hidden}, got {list(t.shape)}")
+            flat[a:b] = t.reshape(-1)
+        flat = flat.to(self.device_)
+        views = {k: flat[at[k][0]:at[k][1]].view(at[k][2]) for k in W.OBJECTNESS_HEAD_KEYS}
+        if trainable:
+            views = {k: v.detach().requires_grad_(True) for k, v in views.items()}          # leaves that share the buffer's storage
+        self._objectness_flat = flat if trainable else None
+        self.objectness_head = views
+        self._objectness_bf16 = {k: ops.cast_bf16(views[k].detach()) for k in ("dense0.weight", "dense1.weight")}
+        return self
+
+    def objectness_head_parameters(self):
+        """The six leaf tensors of a trainable objectness head, in weights.OBJECTNESS_HEAD_KEYS' order, for a torch optimizer of the caller's.  A frozen
+        head, or none, gives an EMPTY list."""
+        oh = getattr(self, "objectness_head", None)
+        if oh is None:
+            return []
+        return [oh[k] for k in W.OBJECTNESS_HEAD_KEYS if oh[k].requires_grad]
+
+    def objectness_head_state(self):
+        """The objectness head in HF's shapes -- float32 numpy, dense0 / dense1 [D, D] and [D], dense2.weight [1, D], dense2.bias [1] -- trained or not: prefix
+        the keys with `objectness_head.` and the six tensors go straight back into an `Owlv2ForObjectDetection` state dict (`load_state_dict` takes them).
+        `set_objectness_head(model.objectness_head_state())` restores the same bits (it takes HF's shapes and weights.hf_objectness_head's alike).  A host
+        copy (it synchronises)."""
+        oh = getattr(self, "objectness_head", None)
+        if oh is None:
+            raise RuntimeError("objectness_head_state: no objectness head -- call model.set_objectness_head(weights.hf_objectness_head(hf_state_dict)) "
+                               "or load_model(..., objectness_head=)")
+        out = OrderedDict()
+        for k in W.OBJECTNESS_HEAD_KEYS:
+            v = oh[k].detach().cpu().numpy().astype(np.float32)
+            out[k] = np.ascontiguousarray(v.reshape(1, -1) if k == "dense2.weight" else v)          # (dense2.bias is held as [1]: HF's shape)
+        return out
+
+    def _need_objectness(self, who):
+        if self.objectness_head is None:
+            raise RuntimeError(f"{who}: no objectness head -- call model.set_objectness_head(weights.hf_objectness_head(hf_state_dict)) or "
+                               "load_model(..., objectness_head=)")
+
+    def _objectness_on(self, feats, h0, h1, out, rows, u0=None, u1=None):
+        """The head on `rows` rows of bf16 features: two erf-GELU GEMMs into h0 / h1 (pre-activations kept in u0 / u1 when given) and the row-dot tail ->
+        out (f32, `rows` elements).  Three launches, one more pair where a trainable head's bf16 weights are re-cast."""
+        oh, wb, D = self.objectness_head, self._objectness_bf16, self.cfg.hidden
+        if self._objectness_flat is not None:
+            for k in wb:
+                ops.cast_bf16(oh[k].detach(), wb[k])
+        ops.gemm(ops.EPI_GELU_BF16, feats, wb["dense0.weight"], h0, bias=oh["dense0.bias"].detach(), aux=u0, M=rows, N=D, K=D)
+        ops.gemm(ops.EPI_GELU_BF16, h0, wb["dense1.weight"], h1, bias=oh["dense1.bias"].detach(), aux=u1, M=rows, N=D, K=D)
+        return ops.objectness_final(h1, oh["dense2.weight"].detach(), oh["dense2.bias"].detach(), out, rows, D)
+
+    def _objectness_ws(self, B):
+        """The head's own activations on the TRAINING path, allocated when first needed at this batch size: h0, u0, h1, u1 bf16 [B P, D] (hb0 / ub0 / hb1 /
+        ub1 belong to the box head's backward)."""
+        key = ("obj", B)
+        if key not in self._ws:
+            Mh, D, z = B * self.cfg.patches, self.cfg.hidden, ops.zeros_rows
+            self._ws[key] = {k: z(Mh, D, torch.bfloat16, self.device_) for k in ("h0", "u0", "h1", "u1")}
+        return self._ws[key]
+
+    def _objectness_train_forward(self, B):
+        """The head on the training workspace's feats (the recording forward of this batch size has just run) -> objectness_logits f32 [B, P]."""
+        ws, ow, P = self._workspace(B), self._objectness_ws(B), self.cfg.patches
+        out = torch.empty(B, P, dtype=torch.float32, device=self.device_)
+        self._objectness_on(ws["feats"], ow["h0"], ow["h1"], out, B * P, u0=ow["u0"], u1=ow["u1"])
+        return out
+
     @torch.no_grad()
-    def detect(self, pixel_values, query_embeds, query_mask=None, return_scores=False):
+    def detect(self, pixel_values, query_embeds, query_mask=None, return_scores=False, objectness=False):
         """Zero-shot detection, HF `OwlViTForObjectDetection` logits: -> (pred_boxes [B, P, 4], logits [B, P, Q]) and, with return_scores=True,
         scores = sigmoid(logits) [B, P, Q] (exactly 0 where masked).  pred_boxes are CORNERS (x0, y0, x1, y1), as everywhere in this project; HF's
         `pred_boxes` are (cx, cy, w, h).
@@ -1018,9 +1124,15 @@ class OwlViT(nn.Module):
 
         Needs `set_logit_head` (RuntimeError otherwise).  Inference only; `forward_queries` is the gradient-recording form.  Runs the plain eval forward on the EVAL
         workspace behind a deferred optimizer tail (a pending training backward is not disturbed), in chunks of at most 32 images; the frozen-prefix
-        cache is neither read nor written; `forward` and its outputs are untouched.  No host sync."""
+        cache is neither read nor written; `forward` and its outputs are untouched.  No host sync.
+
+        objectness=True (OWLv2; needs `set_objectness_head`, RuntimeError otherwise) appends HF's `objectness_logits` f32 [B, P] to the result: the objectness
+        head on each chunk's features, right behind its forward, with its two hidden layers in the eval workspace's box-head buffers (free by then): three
+        launches per chunk and no allocation but the output.  Without the flag no launch and no bit changes, head set or not."""
         if self.logit_head is None:
             raise RuntimeError("detect: no logit head -- call model.set_logit_head(weights.hf_logit_head(hf_state_dict)) or load_model(..., logit_head=)")
+        if objectness:
+            self._need_objectness("detect")
         B, Q, shared = check_detect_args(self.cfg, pixel_values, query_embeds, query_mask)
         cfg, dev, P = self.cfg, self.device_, self.cfg.patches
         qe = torch.as_tensor(query_embeds).to(dev).contiguous()
@@ -1032,6 +1144,7 @@ class OwlViT(nn.Module):
         boxes = torch.empty(B, P, 4, dtype=torch.float32, device=dev)
         logits = torch.empty(B, P, Q, dtype=torch.float32, device=dev)
         scores = torch.empty(B, P, Q, dtype=torch.float32, device=dev) if return_scores else None
+        obj = torch.empty(B, P, dtype=torch.float32, device=dev) if objectness else None
         keep = self.max_cached_batch_sizes          # (as _embed_image_query: no size is evicted by this call)
         self.max_cached_batch_sizes = max(1, int(keep)) + 2
         try:
@@ -1044,19 +1157,22 @@ class OwlViT(nn.Module):
                 ops.class_logits(ws["e"], qe if shared else qe[a:a + nb], ws["feats"], lh["logit_shift.weight"], lh["logit_shift.bias"],
                                  lh["logit_scale.weight"], lh["logit_scale.bias"], nb, P, mask=None if qm is None else (qm if qm.dim() == 1 else qm[a:a + nb]),
                                  rowstats=ws["logit_rowstats"], logits=logits[a:a + nb], scores=scores[a:a + nb] if return_scores else False)
+                if objectness:
+                    self._objectness_on(ws["feats"], ws["hb0"], ws["hb1"], obj[a:a + nb], nb * P)
                 boxes[a:a + nb].copy_(pb)
         finally:
             self.max_cached_batch_sizes = keep
-        return (boxes, logits, scores) if return_scores else (boxes, logits)
+        out = (boxes, logits, scores) if return_scores else (boxes, logits)
+        return out + (obj,) if objectness else out
 
     @torch.no_grad()
-    def detect_text(self, pixel_values, input_ids, text_tower, return_scores=False, shared=None):
+    def detect_text(self, pixel_values, input_ids, text_tower, return_scores=False, shared=None, objectness=False):
         """`detect` on tokenised prompts, HF's `OwlViTForObjectDetection.forward`: input_ids [B Q, S] (HF's layout) or [B, Q, S], Q prompts per image that
         may differ per image, padded queries all-zero ids; or [Q, S] for one list shared by the batch.  A 2-D input whose row count is a multiple of B
         is read as [B Q, S] unless shared=True.  The embeddings are `text_tower.encode(ids)` (text.TextTower: the unit rows HF feeds its head), the
-        mask is ids[..., 0] > 0 as in HF.  -> detect's result."""
+        mask is ids[..., 0] > 0 as in HF.  -> detect's result (objectness=True: with `objectness_logits` appended)."""
         embeds, mask = text_queries("detect_text", int(pixel_values.shape[0]), input_ids, text_tower, shared)
-        return self.detect(pixel_values, embeds, mask, return_scores=return_scores)
+        return self.detect(pixel_values, embeds, mask, return_scores=return_scores, objectness=objectness)
 
     # -- open-vocabulary fine-tuning: the same head, gradient-recording ---------------------------------------------------------
     def _class_logits_on(self, ws, B, qe, qm):
@@ -1067,7 +1183,7 @@ class OwlViT(nn.Module):
         return ops.class_logits(ws["e"], qe, ws["feats"], lh["logit_shift.weight"], lh["logit_shift.bias"], lh["logit_scale.weight"], lh["logit_scale.bias"],
                                 B, P, mask=qm, rowstats=ws["logit_rowstats"])[0]
 
-    def forward_queries(self, pixel_values, query_embeds, query_mask=None):
+    def forward_queries(self, pixel_values, query_embeds, query_mask=None, objectness=False):
         """The gradient-recording form of `detect`: -> (pred_boxes [B, P, 4] corners, logits [B, P, Q]) of HF's class head over the caller's queries,
         arguments as for `detect` (a bank per image [B, Q, Dt] or one shared [Q, Dt], an optional mask; masked logits are finfo(f32).min and pass no
         gradient -- select them out of the loss).  Needs `set_logit_head` (RuntimeError otherwise).
@@ -1082,31 +1198,49 @@ class OwlViT(nn.Module):
         recording forward at the same batch size (RuntimeError otherwise).  The loss over [B, P, Q] logits is
         `losses.OpenVocabLoss` (bipartite matching, sigmoid focal + L1 / GIoU, on device with no host sync), or any torch code of the caller's.
 
-        Under no_grad it is `detect`."""
+        Under no_grad it is `detect`.
+
+        objectness=True (OWLv2; needs `set_objectness_head`) -> (pred_boxes, logits, objectness_logits [B, P]).  With grad enabled the head runs on the
+        training workspace's features with activations of its own.  It reads them DETACHED, as HF does: nothing of it reaches the trunk or flat_grad.  A
+        frozen head's result carries no grad_fn; a trainable head's (set_objectness_head(head, trainable=True)) is the output of
+        autograd.OwlViTObjectnessFunction, whose backward writes the six leaves' gradients -- before, after or without the main backward, same bits -- and
+        is held to the same rule: backward() before the next recording forward at this batch size."""
         if self.logit_head is None:
             raise RuntimeError("forward_queries: no logit head -- call model.set_logit_head(weights.hf_logit_head(hf_state_dict)) or load_model(..., logit_head=)")
+        if objectness:
+            self._need_objectness("forward_queries")
         B, Q, shared = check_detect_args(self.cfg, pixel_values, query_embeds, query_mask)
         qe = torch.as_tensor(query_embeds)
         head = [self.logit_head[k] for k in W.LOGIT_HEAD_KEYS if self.logit_head[k].requires_grad] if self.logit_head else []          # a trainable head's leaves
-        need_grad = torch.is_grad_enabled() and (qe.requires_grad or bool(head) or any(p.requires_grad for p in self.parameters()))
+        obj_leaves = self.objectness_head_parameters() if objectness else []          # (a trainable objectness head alone is reason enough to record)
+        need_grad = torch.is_grad_enabled() and (qe.requires_grad or bool(head) or bool(obj_leaves) or any(p.requires_grad for p in self.parameters()))
         if not need_grad:
-            return self.detect(pixel_values, qe.detach(), query_mask)
+            return self.detect(pixel_values, qe.detach(), query_mask, objectness=objectness)
         self._check_trainable_set()
         qe = qe.to(self.device_).contiguous()          # (autograd-recorded: the gradient finds its way back to the caller's tensor)
         qm = None
         if query_mask is not None:
             qm = (torch.as_tensor(query_mask).to(self.device_) != 0).to(torch.uint8).contiguous()
-        from .autograd import OwlViTQueryFunction
+        from .autograd import OwlViTObjectnessFunction, OwlViTQueryFunction
         if head and len(head) != 4:
             raise RuntimeError("forward_queries: the four logit-head tensors train together or not at all (set_logit_head(head, trainable=True))")
-        return OwlViTQueryFunction.apply(self, pixel_values, qe, qm, *[self._byname[n] for n in self.flat_offsets], *head)
+        out = OwlViTQueryFunction.apply(self, pixel_values, qe, qm, *[self._byname[n] for n in self.flat_offsets], *head)
+        if not objectness:
+            return out
+        leaves = obj_leaves
+        if leaves and len(leaves) != 6:
+            raise RuntimeError("forward_queries: the six objectness-head tensors train together or not at all (set_objectness_head(head, trainable=True))")
+        if leaves:
+            return out + (OwlViTObjectnessFunction.apply(self, B, *leaves),)
+        with torch.no_grad():
+            return out + (self._objectness_train_forward(B),)
 
-    def forward_text(self, pixel_values, input_ids, text_tower, shared=None):
+    def forward_text(self, pixel_values, input_ids, text_tower, shared=None, objectness=False):
         """`forward_queries` on tokenised prompts, input_ids laid out as for `detect_text`.  The text tower stays forward-only: its embeddings are
         detached constants (nothing is trained in it)."""
         with torch.no_grad():
             embeds, mask = text_queries("forward_text", int(pixel_values.shape[0]), input_ids, text_tower, shared)
-        return self.forward_queries(pixel_values, embeds.detach(), mask)
+        return self.forward_queries(pixel_values, embeds.detach(), mask, objectness=objectness)
 
 
 def text_queries(who, B, input_ids, text_tower, shared=None):
@@ -1200,7 +1334,7 @@ def check_exemplars(class_ids, query_boxes, n_images, n_classes):
 
 def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed: int = 1234, state=None, *,
                prompt_ids=None, text_state=None, vocab=None, merges=None, trainable=None, image_size=None, exemplars=None, logit_head=None,
-               logit_head_trainable=False):
+               logit_head_trainable=False, objectness_head=None, objectness_head_trainable=False):
     """ref src/models.py:149-191.  The reference downloads `google/owlvit-base-patch32` and runs the
     CLIP text tower once to initialise the query bank; neither box has network access, so weights
     come from `state` (name -> array, reference parameter names) or, by default, the deterministic
@@ -1233,7 +1367,10 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
     `logit_head` (None = none is set): weights.hf_logit_head(sd), HF's `class_head.logit_shift / logit_scale` -- what zero-shot inference
     (OwlViT.detect / detect_text) needs beside the vision path.  Frozen buffers outside the parameters: see OwlViT.set_logit_head.
     `logit_head_trainable=True` makes them four leaf tensors that `forward_queries`' backward gives gradients (still outside the parameters; stepped
-    by the caller's torch optimizer over `model.logit_head_parameters()`)."""
+    by the caller's torch optimizer over `model.logit_head_parameters()`).
+
+    `objectness_head` (None = none is set): weights.hf_objectness_head(sd), the six `objectness_head.*` tensors of an OWLv2 checkpoint -- what
+    `detect(..., objectness=True)` needs; `objectness_head_trainable=True` makes them six leaf tensors (OwlViT.set_objectness_head)."""
     n_classes = len(labelmap)
     cfg = get_config(arch, n_classes=n_classes)
     g0 = table_grid(np.asarray(state[_POS]).shape[0]) if (state is not None and _POS in state) else cfg.grid
@@ -1271,4 +1408,6 @@ def load_model(labelmap, device="cuda", arch: str = "owlvit-base-patch32", seed:
         model.set_queries_from_exemplars(*exemplars)
     if logit_head is not None:
         model.set_logit_head(logit_head, trainable=logit_head_trainable)
+    if objectness_head is not None:
+        model.set_objectness_head(objectness_head, trainable=objectness_head_trainable)
     return model

@@ -397,11 +397,16 @@ def rowreduce_workspace(groups, rows_per_group, C, device):
     return torch.empty(int(nbytes.item()) // 4, dtype=torch.float32, device=device)
 
 
+def part_floats(rows, C) -> int:
+    """f32 elements of the partial-sum scratch a deterministic column reduction over `rows` rows of `C` columns takes (what _part allocates)."""
+    return ((int(rows) + 63) // 64 + 1) * 6 * max(int(C), 4)
+
+
 def _part(partials, rows, C, device):
     """The caller's scratch, or (stand-alone use: tests, tools) a cached per-device buffer grown on demand."""
     if partials is not None:
         return partials
-    need = ((int(rows) + 63) // 64 + 1) * 6 * max(int(C), 4)
+    need = part_floats(rows, C)
     buf = _partials.get(device)
     if buf is None or buf.numel() < need:
         buf = torch.empty(need, dtype=torch.float32, device=device)
@@ -452,6 +457,37 @@ def box_final_bwd(dboxes, sig, h1, u1, w2, du1, partials, dw2_db2, rows, D, du1_
         raise ValueError("box_final_bwd: partials must hold owl_box_final_bwd_blocks(rows) x (5 D + 4) floats")
     _chk(du1_colsum, torch.float32, "du1_colsum")
     _lib.call("owl_box_final_bwd", stream(), dboxes, sig, h1, u1, w2, du1, partials, dw2_db2, rows, D, du1_colsum)
+
+
+# ---- OWLv2's objectness head, its tail (csrc/objectness.hip) ----
+def objectness_final(h, w2, b2, logits, rows, D):
+    """logits[r] = h[r] . w2 + b2: h bf16 [>= rows, D], w2 f32 [D], b2 f32 one element, logits f32 with at least `rows` elements (written in place)."""
+    _chk(h, torch.bfloat16, "h"); _chk(w2, torch.float32, "w2"); _chk(b2, torch.float32, "b2"); _chk(logits, torch.float32, "logits")
+    rows, D = int(rows), int(D)
+    if h.numel() < rows * D or w2.numel() != D or b2.numel() != 1 or logits.numel() < rows:
+        raise ValueError(f"objectness_final: h must hold [{rows}, {D}], w2 [{D}], b2 one element, logits {rows} elements")
+    _lib.call("owl_objectness_final_fwd", stream(), h, w2, b2, logits, rows, D)
+    return logits
+
+
+def objectness_final_bwd_blocks(rows):
+    return int(_lib.load().owl_objectness_final_bwd_blocks(int(rows)))
+
+
+def objectness_final_bwd(dlogits, h1, u1, w2, du1, partials, dw2_db2, rows, D, du1_colsum=None):
+    """The tail's backward (include/owl_hip.h owl_objectness_final_bwd): dlogits f32 [rows]; h1 / u1 / du1 bf16 [>= rows, D]; partials f32 with
+    objectness_final_bwd_blocks(rows) x (2 D + 4) elements; dw2_db2 f32 [D + 4] = dw2, db2, three zeros; du1_colsum (optional) f32 [D].  Outputs are written,
+    not accumulated into."""
+    _chk(dlogits, torch.float32, "dlogits"); _chk(h1, torch.bfloat16, "h1"); _chk(u1, torch.bfloat16, "u1"); _chk(w2, torch.float32, "w2")
+    _chk(du1, torch.bfloat16, "du1"); _chk(partials, torch.float32, "partials"); _chk(dw2_db2, torch.float32, "dw2_db2"); _chk(du1_colsum, torch.float32, "du1_colsum")
+    rows, D = int(rows), int(D)
+    if dlogits.numel() < rows or min(h1.numel(), u1.numel(), du1.numel()) < rows * D or w2.numel() != D:
+        raise ValueError(f"objectness_final_bwd: dlogits must hold {rows} elements, h1 / u1 / du1 [{rows}, {D}], w2 [{D}]")
+    if partials.numel() < objectness_final_bwd_blocks(rows) * (2 * D + 4):
+        raise ValueError("objectness_final_bwd: partials must hold owl_objectness_final_bwd_blocks(rows) x (2 D + 4) floats")
+    if dw2_db2.numel() < D + 4 or (du1_colsum is not None and du1_colsum.numel() < D):
+        raise ValueError(f"objectness_final_bwd: dw2_db2 must hold {D + 4} floats (dw2, db2, three zeros), du1_colsum {D}")
+    _lib.call("owl_objectness_final_bwd", stream(), dlogits, h1, u1, w2, du1, partials, dw2_db2, rows, D, du1_colsum)
 
 
 # ---- the box head's dX GEMMs on the rows that carry a gradient (csrc/box_rows_bwd.hip) ----

@@ -47,6 +47,22 @@ def unpad_boxes(boxes, sizes, to="pixels"):
     return (boxes.double() * torch.stack([fx, fy, fx, fy], dim=-1).unsqueeze(-2)).to(boxes.dtype)
 
 
+def top_objects(pred_boxes, objectness_logits, k):
+    """OWLv2's class-agnostic proposals, "the k best objects first": pred_boxes [B, P, 4], objectness_logits [B, P] (`detect(..., objectness=True)`) ->
+    (boxes [B, k, 4], scores [B, k] = sigmoid(objectness_logits), patch [B, k] i64) in the order of `torch.sort(scores, stable=True, descending=True)`:
+    equal scores keep the lower patch index first.  It is `owl_postprocess` on a one-class score with a confidence threshold below every score and an IoU
+    threshold nothing exceeds (no suppression): no new kernel, no host sync.  A NaN logit drops its patch, as torch.max's rule drops it everywhere in the
+    post-process: the tail of that image is then padded (boxes 0, scores 0, patch -1).  1 <= k <= P."""
+    if pred_boxes.dim() != 3 or pred_boxes.shape[-1] != 4 or objectness_logits.dim() != 2 or tuple(objectness_logits.shape) != tuple(pred_boxes.shape[:2]):
+        raise ValueError(f"top_objects: expected pred_boxes [B, P, 4] and objectness_logits [B, P], got {tuple(pred_boxes.shape)} / {tuple(objectness_logits.shape)}")
+    P = int(objectness_logits.shape[1])
+    if not 1 <= int(k) <= P:
+        raise ValueError(f"top_objects: 1 <= k <= {P} patches, got {k}")
+    scores = torch.sigmoid(objectness_logits.detach().float())
+    boxes, _, top, patch, _ = ops.postprocess(pred_boxes.detach().float().contiguous(), scores.unsqueeze(-1).contiguous(), int(k), -1.0, 1.0, "per_class")
+    return boxes, top, patch
+
+
 class PostProcess:
     def __init__(self, confidence_threshold=0.75, iou_threshold=0.3, *, nms_route="torchvision_gpu"):   # ref models.py:123-125 (same defaults)
         if nms_route not in ops.NMS_ROUTES:

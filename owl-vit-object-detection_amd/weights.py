@@ -264,7 +264,7 @@ def from_hf_state_dict(sd, queries=None) -> "OrderedDict[str, np.ndarray]":
 
     An `Owlv2ForObjectDetection.state_dict()` is the same dict under the prefix `owlv2.` in place of `owlvit.` (the vision tower, the encoder layers and
     both heads are source-identical after renaming), plus six `objectness_head.*` tensors.  Both prefixes are taken; `objectness_head.*` is skipped like
-    the other tensors this path does not own (the objectness head is not built).  Such a checkpoint expects `DeviceImageProcessor(resize="owlv2")`."""
+    the other tensors this path does not own (`hf_objectness_head` takes them, for `OwlViT.set_objectness_head`). Such a checkpoint expects `DeviceImageProcessor(resize="owlv2")`."""
     out = OrderedDict()
 
     def arr(v):
@@ -317,6 +317,36 @@ def hf_logit_head(sd) -> "OrderedDict[str, np.ndarray]":
         out[k] = np.ascontiguousarray(v.reshape(-1)) if k.endswith("weight") else v.reshape(()).copy()          # (ascontiguousarray would make a scalar 1-d)
     if out["logit_shift.weight"].shape != out["logit_scale.weight"].shape:
         raise ValueError("hf_logit_head: logit_shift.weight and logit_scale.weight differ in size")
+    return out
+
+
+OBJECTNESS_HEAD_KEYS = ("dense0.weight", "dense0.bias", "dense1.weight", "dense1.bias", "dense2.weight", "dense2.bias")
+
+
+def hf_objectness_head(sd) -> "OrderedDict[str, np.ndarray]":
+    """The six tensors of HF's `objectness_head` (Owlv2BoxPredictionHead(out_dim=1): three Linear layers, D -> D -> D -> 1) out of an
+    `Owlv2ForObjectDetection.state_dict()`, which `from_hf_state_dict` skips: {"dense0.weight" [D, D], "dense0.bias" [D], "dense1.weight" [D, D],
+    "dense1.bias" [D], "dense2.weight" [D], "dense2.bias" []}, float32 ndarrays.  They are NOT parameters of the model: hand them to
+    `OwlViT.set_objectness_head` / `load_model(..., objectness_head=)`.  Values may be torch tensors or arrays; a missing tensor raises KeyError naming
+    it (an OWL-ViT checkpoint has no objectness head: only OWLv2 ships one)."""
+    out = OrderedDict()
+    for k in OBJECTNESS_HEAD_KEYS:
+        key = "objectness_head." + k
+        if key not in sd:
+            raise KeyError(f"hf_objectness_head: `{key}` is not in the state dict (an OWL-ViT checkpoint has no objectness head: only "
+                           "Owlv2ForObjectDetection ships one)")
+        v = sd[key]
+        if hasattr(v, "detach"):
+            v = v.detach().to("cpu").float().numpy()
+        v = np.asarray(v, dtype=np.float32)
+        if k == "dense2.weight":
+            v = v.reshape(-1)
+        out[k] = v.reshape(()).copy() if k == "dense2.bias" else np.ascontiguousarray(v)
+    D = out["dense2.weight"].shape[0]
+    for k in OBJECTNESS_HEAD_KEYS[:4]:
+        want = (D, D) if k.endswith("weight") else (D,)
+        if out[k].shape != want:
+            raise ValueError(f"hf_objectness_head: `objectness_head.{k}` has shape {out[k].shape}, expected {want} beside dense2.weight [{D}]")
     return out
 
 
